@@ -11,7 +11,13 @@ CorrectCone rows per image, N=32,768 rows) = the reference's training_step + bac
   metric scalars]  ->  Adam.
 Inputs are synthetic (x ~ U[0,1), y ~ randint(10), seeded), resident in HBM before timing.
 
-Besides the JSON fields of the contract, the line carries:
+A plain run sets up, warms up, times the K steps and prints the JSON line of the contract (value,
+ms_per_step, ...).  ``--dump-outputs DIR`` then also writes what the last timed step computed (the
+loss, the fused metric scalars, the updated parameters) as DIR/<name>.npy: the inputs, the initial
+parameters and the Philox seed are fixed, so two builds can be compared array for array.
+
+With ``--full`` the line also carries the companion measurements (the Lyapunov-only, dopri5,
+certification and B=1024 workloads, each timed in a run of its own) and:
   roofline      the dominant fused kernel's algorithmic FLOP / its mean duration (HIP events
                 recorded by libfiode on the kernels' stream) vs the f32 MFMA peak
   cpu_baseline  the same step on the host cores (backbone + Cayley maps + the reference fan-out
@@ -175,6 +181,32 @@ def load_pmc(kernel: str) -> dict:
             "lds_bank_conflict_frac": k.get("lds_bank_conflict_frac"), "pmc_source": d.get("_source")}
 
 
+DUMP_BUDGET_BYTES = 60 << 20      # all of --dump-outputs stays under 64 MB
+
+
+def dump_outputs(out_dir, arrays: dict, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """Write ``arrays`` (name -> tensor / ndarray) as ``out_dir/<name>.npy`` in float32 (float64
+    stays float64).  Over ``budget`` bytes in all, every array above 4,096 elements is cut to the same
+    fraction of its (flattened) elements, picked by a generator seeded with the array's size, so two
+    runs keep the same elements.  Returns name -> the array written."""
+    import numpy as np
+    out_dir = pathlib.Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    small = sum(a.nbytes for a in host.values() if a.size <= 4096)
+    large = sum(a.nbytes for a in host.values() if a.size > 4096)
+    frac = 1.0 if small + large <= budget else max(0.0, (budget - small) / large)
+    for name, a in host.items():
+        if frac < 1.0 and a.size > 4096:
+            keep = np.random.default_rng(a.size).choice(a.size, size=int(a.size * frac), replace=False)
+            a = host[name] = a.reshape(-1)[np.sort(keep)]
+        np.save(out_dir / f"{name}.npy", a)
+    return host
+
+
 def _free_port() -> int:
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -222,6 +254,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline step: the companion workloads, the per-kernel / roofline timing "
+                         "and the CPU baseline (each can be switched off with its --no-... option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, metric scalars, updated "
+                         "parameters) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=25.0)
     ap.add_argument("--prof-reps", type=int, default=20)
@@ -249,8 +287,9 @@ def main():
     torch.cuda.set_device(dev)
 
     def timed_run(train_ode: bool, steps: int, warmup: int, solver: str = "rk4", batch: int = B_PER_RANK,
-                  h_sample: int = H_SAMPLE, strict: bool = True):
-        """Build the module, capture (or not) the step, run warmup + timed steps; max over ranks."""
+                  h_sample: int = H_SAMPLE, strict: bool = True, dump_dir=None):
+        """Build the module, capture (or not) the step, run warmup + timed steps; max over ranks.
+        ``dump_dir``: rank 0 writes what the last timed step computed there (dump_outputs)."""
         mod = build_module(dev, seed=0, train_ode=train_ode, solver=solver, h_sample=h_sample)
         mod.seed = 1000 + rank                      # each rank draws its own samples / dropout masks
         opt = mod.configure_optimizers(capturable=not args.eager)[0][0]
@@ -332,6 +371,13 @@ def main():
         if last.get("placement_ms") is not None:
             health["placement_ms"] = last["placement_ms"]     # per trial capture; the fastest is kept
             health["placement_recaptures"] = last.get("recaptures", 0)
+        if dump_dir is not None and rank == 0:
+            # what a caller of the step holds after it: the loss it returns, the fused metric scalars
+            # (training_loss, effective_batch_size, mean_active_constraints, ...) and the parameters
+            # the step's Adam update left behind
+            arrays = {"loss": last["loss"], "scalars": mod.last_plan["scalars"]}
+            arrays.update({"param." + k: p for k, p in mod.named_parameters()})
+            dump_outputs(dump_dir, arrays)
         return float(dt.item()), mod, x, y, health
 
     def certify_companion(n_img: int = 2):
@@ -373,11 +419,11 @@ def main():
                             "time (all four kernels)"}
 
     train_ode = args.workload == "rk4"
-    elapsed, mod, x, y, health = timed_run(train_ode, args.steps, args.warmup)
+    elapsed, mod, x, y, health = timed_run(train_ode, args.steps, args.warmup, dump_dir=args.dump_outputs)
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B_PER_RANK * args.steps / elapsed
     lyap_only = dopri5_step = None
-    if train_ode and not args.no_secondary:
+    if args.full and train_ode and not args.no_secondary:
         e2, _, _, _, _ = timed_run(False, args.steps, args.warmup)
         lyap_only = {"images_per_s": round(world * B_PER_RANK * args.steps / e2, 2),
                      "ms_per_step": round(e2 / args.steps * 1e3, 4)}
@@ -391,7 +437,7 @@ def main():
                        "workload": "BASELINE configs[2]: the configs[1] step with train_ode_solver dopri5, "
                                    "train_ode_tol 1e-3 (rtol = atol), direct backprop through the adaptive solve"}
     certify_line = large_batch = None
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         certify_line = certify_companion()
         # BASELINE configs[4]: B=1024 images x h_sample 1024 per rank, train_ode dopri5 (tol 1e-3),
         # backbone + Cayley maps + Adam, DDP over the ranks (the same bucketed all-reduce)
@@ -408,65 +454,70 @@ def main():
         del m4
         torch.cuda.empty_cache()
 
-    # ---- per-kernel timing of the fused hot path with HIP events (same inputs as a step) ----
-    from fiode_amd import _lib as L, ops
-    with torch.no_grad():
-        feat = mod.init_coordinates.param_map(x).float().contiguous()
-        w = {k: v.detach().float().contiguous() for k, v in mod.dyn_fun.effective_weights().items()}
-    plan = mod.step_plan(y)
-    nk = len(L.LYAP_KERNELS)
-    tot = [0.0] * nk
-    for r in range(args.prof_reps + 2):
-        evs = [torch.cuda.Event(enable_timing=True) for _ in range(nk + 1)]
-        torch.cuda._sleep(4_000_000)
-        ops.lyap_step(feat, y, w, plan["dyn"], sample_size=plan["S"], n_uniform=plan["S1"], sampler=plan["sampler"],
-                      dropout_mode=plan["dropout_mode"], kappa=plan["kappa"], seed=plan["seed"], offset=r, events=evs)
-        torch.cuda.synchronize()
-        if r >= 2:
-            for i in range(nk):
-                tot[i] += evs[i].elapsed_time(evs[i + 1])
-    kern_ms = {L.LYAP_KERNELS[i]: tot[i] / args.prof_reps for i in range(nk)}
-    rows = B_PER_RANK * H_SAMPLE
-    kern_flop = {k: FLOP_ROW[k] * rows for k in FLOP_ROW}
-    if train_ode:
-        # the differentiable RK4 solve: k_ot_fwd (one kernel) and k_ot_bwd + its wgrad chain
-        oplan = mod.ode_plan(B_PER_RANK)
-        h0 = torch.full((B_PER_RANK, 10), 0.1, device=dev)
-        E = ops.odetrain_evals(oplan["cfg"])
-        t_f = t_b = 0.0
+    def kernel_profile():
+        """--full: per-kernel timing of the fused hot path with HIP events (same inputs as a step)."""
+        from fiode_amd import _lib as L, ops
+        with torch.no_grad():
+            feat = mod.init_coordinates.param_map(x).float().contiguous()
+            w = {k: v.detach().float().contiguous() for k, v in mod.dyn_fun.effective_weights().items()}
+        plan = mod.step_plan(y)
+        nk = len(L.LYAP_KERNELS)
+        tot = [0.0] * nk
         for r in range(args.prof_reps + 2):
-            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-            # keep the stream busy while the host enqueues, so e0..e2 time GPU work only (not the
-            # host's allocation / argument packing between the event records)
+            evs = [torch.cuda.Event(enable_timing=True) for _ in range(nk + 1)]
             torch.cuda._sleep(4_000_000)
-            e0.record()
-            yo, _, ws = ops.odetrain_forward(feat, h0, w, oplan["dyn"], oplan["cfg"], offset_dev=oplan["offset_dev"])
-            e1.record()
-            ops.odetrain_backward(torch.ones_like(yo), feat, w, oplan["dyn"], oplan["cfg"], ws)
-            e2.record()
+            ops.lyap_step(feat, y, w, plan["dyn"], sample_size=plan["S"], n_uniform=plan["S1"], sampler=plan["sampler"],
+                          dropout_mode=plan["dropout_mode"], kappa=plan["kappa"], seed=plan["seed"], offset=r, events=evs)
             torch.cuda.synchronize()
             if r >= 2:
-                t_f += e0.elapsed_time(e1)
-                t_b += e1.elapsed_time(e2)
-        # the forward launched at this batch: 4-row tiles (k_ot_fwd4) up to 1,024 rows (odetrain.hip)
-        fwd_name = "k_ot_fwd4" if (B_PER_RANK + 3) // 4 <= 256 else "k_ot_fwd"
-        kern_ms[fwd_name] = t_f / args.prof_reps
-        kern_ms["k_ot_bwd+wgrad"] = t_b / args.prof_reps
-        kern_flop[fwd_name] = FLOP_ROW_FWD_PASS * E * B_PER_RANK
-        kern_flop["k_ot_bwd+wgrad"] = (2 * (10 * 128 + 128 * 128 + 128 * 10) + FLOP_ROW_FWD_PASS) * E * B_PER_RANK
-    hot_ms = sum(kern_ms.values())
-    dom = max(kern_flop, key=lambda k: kern_ms[k])
-    ach = kern_flop[dom] / (kern_ms[dom] * 1e-3) / 1e12
-    pmc = load_pmc(dom)
-    roofline = {"bound": "mfma", "achieved": round(ach, 3), "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(ach / MFMA_F32_PEAK_TFLOPS, 4), "traffic": pmc.get("traffic"),
-                "mfma_busy": pmc.get("mfma_busy"), "lds_bank_conflict_frac": pmc.get("lds_bank_conflict_frac"),
-                "pmc_source": pmc.get("pmc_source"), "kernel": dom,
-                "kernel_ms": round(kern_ms[dom], 4), "flop_per_launch": kern_flop[dom],
-                "per_kernel_ms": {k: round(v, 4) for k, v in kern_ms.items()},
-                "per_kernel_tflops": {k: round(kern_flop[k] / (kern_ms[k] * 1e-3) / 1e12, 3)
-                                      for k in kern_flop},
-                "hot_path_tflops": round(sum(kern_flop.values()) / (hot_ms * 1e-3) / 1e12, 3)}
+                for i in range(nk):
+                    tot[i] += evs[i].elapsed_time(evs[i + 1])
+        kern_ms = {L.LYAP_KERNELS[i]: tot[i] / args.prof_reps for i in range(nk)}
+        kern_flop = {k: FLOP_ROW[k] * rows for k in FLOP_ROW}
+        if train_ode:
+            # the differentiable RK4 solve: k_ot_fwd (one kernel) and k_ot_bwd + its wgrad chain
+            oplan = mod.ode_plan(B_PER_RANK)
+            h0 = torch.full((B_PER_RANK, 10), 0.1, device=dev)
+            E = ops.odetrain_evals(oplan["cfg"])
+            t_f = t_b = 0.0
+            for r in range(args.prof_reps + 2):
+                e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+                # keep the stream busy while the host enqueues, so e0..e2 time GPU work only (not the
+                # host's allocation / argument packing between the event records)
+                torch.cuda._sleep(4_000_000)
+                e0.record()
+                yo, _, ws = ops.odetrain_forward(feat, h0, w, oplan["dyn"], oplan["cfg"], offset_dev=oplan["offset_dev"])
+                e1.record()
+                ops.odetrain_backward(torch.ones_like(yo), feat, w, oplan["dyn"], oplan["cfg"], ws)
+                e2.record()
+                torch.cuda.synchronize()
+                if r >= 2:
+                    t_f += e0.elapsed_time(e1)
+                    t_b += e1.elapsed_time(e2)
+            # the forward launched at this batch: 4-row tiles (k_ot_fwd4) up to 1,024 rows (odetrain.hip)
+            fwd_name = "k_ot_fwd4" if (B_PER_RANK + 3) // 4 <= 256 else "k_ot_fwd"
+            kern_ms[fwd_name] = t_f / args.prof_reps
+            kern_ms["k_ot_bwd+wgrad"] = t_b / args.prof_reps
+            kern_flop[fwd_name] = FLOP_ROW_FWD_PASS * E * B_PER_RANK
+            kern_flop["k_ot_bwd+wgrad"] = (2 * (10 * 128 + 128 * 128 + 128 * 10) + FLOP_ROW_FWD_PASS) * E * B_PER_RANK
+        hot_ms = sum(kern_ms.values())
+        dom = max(kern_flop, key=lambda k: kern_ms[k])
+        ach = kern_flop[dom] / (kern_ms[dom] * 1e-3) / 1e12
+        pmc = load_pmc(dom)
+        roofline = {"bound": "mfma", "achieved": round(ach, 3), "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": round(ach / MFMA_F32_PEAK_TFLOPS, 4), "traffic": pmc.get("traffic"),
+                    "mfma_busy": pmc.get("mfma_busy"), "lds_bank_conflict_frac": pmc.get("lds_bank_conflict_frac"),
+                    "pmc_source": pmc.get("pmc_source"), "kernel": dom,
+                    "kernel_ms": round(kern_ms[dom], 4), "flop_per_launch": kern_flop[dom],
+                    "per_kernel_ms": {k: round(v, 4) for k, v in kern_ms.items()},
+                    "per_kernel_tflops": {k: round(kern_flop[k] / (kern_ms[k] * 1e-3) / 1e12, 3)
+                                          for k in kern_flop},
+                    "hot_path_tflops": round(sum(kern_flop.values()) / (hot_ms * 1e-3) / 1e12, 3)}
+        hot = {"ms": round(hot_ms, 4), "images_per_s": round(world * B_PER_RANK / (hot_ms * 1e-3), 1)}
+        return roofline, hot
+
+    rows = B_PER_RANK * H_SAMPLE
+    roofline, hot_path = kernel_profile() if args.full else (None, None)
     out = {"metric": METRIC, "value": round(value, 2), "unit": "images/s", "n_gpus": world, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "f32", "data": "synthetic (x~U[0,1) 128x3x32x32 per rank, y~randint(10))",
@@ -480,7 +531,7 @@ def main():
                       "global_batch": world * B_PER_RANK, "h_sample_size": H_SAMPLE,
                       "rows_per_rank": rows, "parallelism": f"dp{world}"},
            "roofline": roofline,
-           "hot_path": {"ms": round(hot_ms, 4), "images_per_s": round(world * B_PER_RANK / (hot_ms * 1e-3), 1)},
+           "hot_path": hot_path,
            "lyapunov_only_step": lyap_only,
            "dopri5_train_step": dopri5_step,
            "certify_T40": certify_line,
@@ -489,7 +540,7 @@ def main():
                              dist.get_world_size() if world > 1 else 1},
            "device_status": health,
            "runtime_env": {"DEBUG_HIP_FORCE_GRAPH_QUEUES": os.environ.get("DEBUG_HIP_FORCE_GRAPH_QUEUES")}}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_budget, train_ode=train_ode)
     else:
         out["cpu_baseline"] = None

@@ -13,5 +13,5 @@ timeout -k 10 120 python tools/ab_odetrain.py $O/ab_new.pt >> $O/ab.log 2>&1 || 
 python tools/ab_odetrain.py --cmp $O/ab_base.pt $O/ab_new.pt >> $O/ab.log 2>&1; echo "ab cmp rc=$?"; cat $O/ab.log
 timeout -k 10 180 python tools/ot_probe.py > $O/ot_probe.log 2>&1 || { echo "ot_probe rc=$?"; exit 1; }
 cat $O/ot_probe.log
-timeout -k 10 400 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { echo "bench rc=$?"; exit 1; }
+timeout -k 10 400 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { echo "bench rc=$?"; exit 1; }
 python -c "import json; d=json.loads(open('$O/bench.json').read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['per_kernel_ms'], d.get('dopri5_train_step'))"

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for d in . "$1"; do
   t=$(basename $(cd $d && pwd))
   (cd $d && timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$O/tr_$t -o run -- \
-      python bench.py --steps 30) > $O/$t.log 2>&1
+      python bench.py --full --steps 30) > $O/$t.log 2>&1
   f=$(find $O/tr_$t -name "run_kernel_trace.csv" | head -1)
   python tools/window_stats.py $f --json $O/$t.json > $O/$t.txt
   rm -rf $O/tr_$t

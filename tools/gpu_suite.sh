@@ -12,6 +12,6 @@ tail -3 $O/suite.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 \
     || { echo "smoke failed rc=$?"; tail -20 $O/smoke.log; exit 1; }
 cat $O/smoke.log
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err \
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err \
     || { echo "bench failed rc=$?"; tail -20 $O/bench.err; exit 1; }
 cat $O/bench.json

@@ -10,7 +10,7 @@ for round in $(seq 1 $R); do
   for v in base "$@"; do
     i=$((i+1))
     if [ $v = base ]; then E=""; elif [[ $v == *=* ]]; then E="$v"; else E="$v=1"; fi
-    env $E timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-configs --no-secondary \
+    env $E timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-configs --no-secondary \
         > $O/${i}_${v//=/-}.json 2>/dev/null || { echo "fail $v"; exit 1; }
     echo "$i $v done"
   done

@@ -99,7 +99,7 @@ def main(src: str, dst: str):
     shutil.copy(stats, f"{dst}_kernel_stats.csv")
     total = sum(float(r["TotalDurationNs"]) for r in rows)
     lines = [f"# rocprofv3 --kernel-trace --stats  ({src_p.name})", "",
-             "Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 10 "
+             "Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --steps 10 "
              "--warmup 3 --no-cpu-baseline --no-secondary` (tools/gpu_profile.sh; the step is a hipGraph replay, "
              "the fused kernels are also launched once more per rep by bench.py's per-kernel HIP-event timing).", "",
              f"Total kernel time {total / 1e6:.2f} ms over {sum(int(r['Calls']) for r in rows)} dispatches "
@@ -148,7 +148,7 @@ def main(src: str, dst: str):
                 f = lambda x: "-" if x is None else f"{x:.4f}"
                 lines.append(f"| {k} | {f(v.get('mfma_busy_frac'))} | {f(v.get('busy_over_expected'))} | "
                              f"{f(v.get('lds_bank_conflict_frac'))} |")
-        summ["_source"] = (f"rocprofv3 --pmc passes of `bench.py --steps 2 --warmup 1` ({src_p.name}; "
+        summ["_source"] = (f"rocprofv3 --pmc passes of `bench.py --full --steps 2 --warmup 1` ({src_p.name}; "
                            "tools/gpu_profile.sh), not the timed run")
         (dst_p.parent / "pmc_summary.json").write_text(json.dumps(summ, indent=1))
     bj = src_p / "bench.json"
