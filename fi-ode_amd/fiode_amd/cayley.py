@@ -14,14 +14,13 @@ from __future__ import annotations
 
 import ctypes as ct
 import math
-import os
 from typing import Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .streams import new_stream
+from .streams import current, fork, join, prefetch, run_on, shared, take
 
 
 _BLOCK = 128
@@ -302,14 +301,15 @@ class _DenseCayleyFn(torch.autograd.Function):
             Q = _dense_finish(st, inv)
         ctx.save_for_backward(st["Wb"], st["al"], st["nrm"], inv)
         ctx.shapes = (W.shape, alpha.shape)
-        ctx.step_stream = STEP_STREAM
+        ctx.step_stream = current().step
         return Q.reshape(W.shape)
 
     @staticmethod
     def backward(ctx, gQ):
+        # on the stream the step was launched from, not the prefetch stream the forward ran on
+        # ("Backward placement" below)
         Wb, al, nrm, inv = ctx.saved_tensors
-        return _run_on_step_stream(DENSE_BWD_ON_MAIN, ctx.step_stream,
-                                   lambda: _dense_backward(Wb, al, nrm, inv, gQ, *ctx.shapes))
+        return run_on(ctx.step_stream, lambda: _dense_backward(Wb, al, nrm, inv, gQ, *ctx.shapes))
 
 
 class _SmallCayleyFn(torch.autograd.Function):
@@ -332,15 +332,10 @@ class _SmallCayleyFn(torch.autograd.Function):
                 "fiode_small_cayley_forward")
         ctx.save_for_backward(Wb, al, nrm, inv)
         ctx.shapes = (W.shape, alpha.shape)
-        ctx.step_stream = STEP_STREAM
         return Q.reshape(W.shape)
 
     @staticmethod
     def backward(ctx, gQ):
-        return _run_on_step_stream(SMALL_BWD_ON_MAIN, ctx.step_stream, lambda: _SmallCayleyFn._backward(ctx, gQ))
-
-    @staticmethod
-    def _backward(ctx, gQ):
         from . import ops, _lib as L
         Wb, al, nrm, inv = ctx.saved_tensors
         wshape, ashape = ctx.shapes
@@ -401,74 +396,14 @@ def cayley(W: torch.Tensor) -> torch.Tensor:
 
 
 # Backward placement of the prefetched maps.  autograd runs a node's backward on the stream its
-# forward ran on (a side stream); with these flags the backward of the spectral / dense maps runs
-# on the stream the step was launched from instead: STEP_STREAM is set by
-# LyapunovLearning.compute_loss only while it runs (step_stream_scope) and each map records it on
-# its autograd ctx at forward time, so a later eager or non-parallel step never sends work to a
-# stale (e.g. graph-capture) stream.  The hipGraph executor places that stream on another
-# hardware queue.  With the executor on 2 internal
-# streams (bench.py) the dense maps' backward on the step stream measured 2.28 -> 2.24 ms per step
-# in the interleaved A/B (tools/ab_step.py); the spectral maps' is slower there (2.35 ms).
-SPECTRAL_BWD_ON_MAIN = False
-DENSE_BWD_ON_MAIN = True
+# forward ran on (a side stream).  The dense maps' backward runs on the stream the step was launched
+# from instead (streams.StepStreams.step, set by LyapunovLearning.compute_loss only while it runs;
+# each map records it on its autograd ctx at forward time).  The hipGraph executor places that stream
+# on another hardware queue.  With the executor on 2 internal streams (bench.py) the dense maps'
+# backward on the step stream measured 2.28 -> 2.24 ms per step in the interleaved A/B
+# (tools/ab_step.py); the spectral maps' is slower there (2.35 ms) and stays on its forward's stream.
 DENSE_GEMM = True          # GMn by fiode_dense_gemm (tools/ab_step.py `lib_gmn` measures the library form)
 DENSE_NORM_PARTIALS = True  # ||W|| by fiode_dense_norm_partials + the prep kernel (`torch_norm`: vector_norm)
-SMALL_BWD_ON_MAIN = False
-STEP_STREAM: Optional[torch.cuda.Stream] = None
-
-
-class step_stream_scope:
-    """Context manager: STEP_STREAM = ``stream`` inside, the previous value restored on exit."""
-
-    def __init__(self, stream):
-        self.stream = stream
-
-    def __enter__(self):
-        global STEP_STREAM
-        self.prev, STEP_STREAM = STEP_STREAM, self.stream
-        return self
-
-    def __exit__(self, *exc):
-        global STEP_STREAM
-        STEP_STREAM = self.prev
-        return False
-
-
-def _run_on_step_stream(flag: bool, step_stream, fn):
-    tgt = step_stream if flag else None
-    cur = torch.cuda.current_stream()
-    if tgt is None or tgt == cur:
-        return fn()
-    tgt.wait_stream(cur)
-    with torch.cuda.stream(tgt):
-        out = fn()
-    cur.wait_stream(tgt)
-    for t in out:
-        if isinstance(t, torch.Tensor):
-            t.record_stream(cur)
-    return out
-
-
-def _prefetch(stream: torch.cuda.Stream, fn):
-    """Run fn() on `stream` (forked from the current stream); returns (result, done event)."""
-    main = torch.cuda.current_stream(stream.device)
-    stream.wait_stream(main)
-    with torch.cuda.stream(stream):
-        out = fn()
-        ev = torch.cuda.Event()
-        ev.record(stream)
-    return out, ev
-
-
-def _take(pre):
-    """Join a prefetched result into the current stream."""
-    out, ev = pre
-    main = torch.cuda.current_stream()
-    main.wait_event(ev)
-    for t in (out.values() if isinstance(out, dict) else (out,)):
-        if isinstance(t, torch.Tensor):
-            t.record_stream(main)
-    return out
 
 
 class CayleyLinear(nn.Linear):
@@ -494,12 +429,12 @@ class CayleyLinear(nn.Linear):
     def prefetch(self, stream: torch.cuda.Stream) -> None:
         """Compute this step's Cayley map on a side stream (its latency-bound inverse overlaps
         the layers before it); the next training forward joins it."""
-        self._pre = _prefetch(stream, self.effective_weight)
+        self._pre = prefetch(stream, self.effective_weight)
 
     def forward_weight_unjoined(self):
         """(Q, done event or None): forward_weight, but a pending prefetched map is handed out
         WITHOUT making the current stream wait for it -- the caller waits on the event right before
-        its first use of Q (the stream-order bookkeeping of _take is done here)."""
+        its first use of Q (the stream-order bookkeeping of streams.take is done here)."""
         if self._pre is not None and self.training:
             (Q, ev), self._pre = self._pre, None
             Q.record_stream(torch.cuda.current_stream(Q.device))
@@ -510,7 +445,7 @@ class CayleyLinear(nn.Linear):
     def forward_weight(self) -> torch.Tensor:
         """The effective weight this forward uses (the prefetched map when one is pending)."""
         if self._pre is not None and self.training:
-            Q = _take(self._pre)
+            Q = take(self._pre)
             self._pre = None
         elif self.training or self._Q is None:
             Q = self.effective_weight()
@@ -527,24 +462,17 @@ class CayleyLinear(nn.Linear):
 
 # KWLargeConcat's head (Linear -> GroupSort -> Linear -> GroupSort -> Linear) as one autograd node
 # whose backward keeps only the input-gradient chain on the step's stream (see _LinearHeadFn)
-HEAD_WGRAD_SIDE = os.environ.get("FIODE_HEAD_WGRAD_SIDE", "1") != "0"
-_HEAD_STREAMS: dict = {}
+HEAD_WGRAD_SIDE = True       # False: module by module (autograd's addmm backward; the tests' reference)
 
 
-# side streams of the head's weight gradients: 3 = one stream per layer (the step's stream joins
-# them all at the end of the head's backward; layer 3's is also the conv weight gradients' stream).
-# With 1 the three layers' products and bias sums ran in sequence on one stream, and that ~55 us
-# chain, not the input-gradient chain, was the head backward's part of the step's dependency path
+# side streams of the head's weight gradients: one per layer (the step's stream joins them all at
+# the end of the head's backward; layer 3's is also the conv weight gradients' stream).  On one
+# stream the three layers' products and bias sums ran in sequence, and that ~55 us chain, not the
+# input-gradient chain, was the head backward's part of the step's dependency path
 # (profiles/r06/dag_warm/): 3 streams measured 8-23 us faster per step, 2 streams or the bias sums on
 # three more streams slower (profiles/r06/ab_head_wgrad_streams.json)
-HEAD_WGRAD_STREAMS = int(os.environ.get("FIODE_HEAD_WGRAD_STREAMS", "3"))
-
-
 def _head_stream(dev: torch.device, k: int = 0) -> torch.cuda.Stream:
-    key = (dev.index, k % HEAD_WGRAD_STREAMS)
-    if key not in _HEAD_STREAMS:
-        _HEAD_STREAMS[key] = new_stream(dev)
-    return _HEAD_STREAMS[key]
+    return shared(dev, f"head_wgrad{k % 3}")
 
 
 class _LinearHeadFn(torch.autograd.Function):
@@ -553,8 +481,8 @@ class _LinearHeadFn(torch.autograd.Function):
     sum in sequence on one stream, so the next layer's input gradient waited for the weight
     gradient it does not need (the head's backward is on the step's critical path).  Here the
     weight / bias gradients (the same GEMM g^T x and column sum) of every layer run on a side
-    stream of their own (HEAD_WGRAD_STREAMS) forked as soon as that layer's output gradient exists,
-    beside the input-gradient chain, and join the step's stream once at the end.  The products go through ops.mm (the library GEMM
+    stream of their own (_head_stream) forked as soon as that layer's output gradient exists, beside the
+    input-gradient chain, and join the step's stream once at the end.  The products go through ops.mm (the library GEMM
     at this site: ops.MM_LIBRARY_SITES), the output layer fiode_head_out / _backward_gs when it has
     <= 16 outputs (KWLargeConcat's 10 classes; a wider out_dim, e.g. make_ortho_KWLarge_Concat's
     default 128, takes ops.mm + the GroupSort kernel)."""
@@ -586,32 +514,18 @@ class _LinearHeadFn(torch.autograd.Function):
         from . import ops
         h, Q1, Q2, Q3, y1, z1, y2, z2 = ctx.saved_tensors
         g = g.contiguous()
-        cur = torch.cuda.current_stream(g.device)
-        sides = []
-        wg = {}
 
         def wgrad(k, gk, x):
-            side = _head_stream(g.device, k)
-            if side not in sides:
-                sides.append(side)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                wg[k] = (ops.mm(gk.t(), x, site="head"), gk.sum(0))
-            gk.record_stream(side)
-            x.record_stream(side)
+            return fork(_head_stream(g.device, k), lambda: (ops.mm(gk.t(), x, site="head"), gk.sum(0)), reads=(gk, x))
 
-        wgrad(3, g, z2)
+        w3 = wgrad(3, g, z2)
         g2 = ops.head_out_backward_gs(g, Q3, y2) if ctx.out_k else ops.groupsort_backward(y2, ops.mm(g, Q3, site="head"), 1)
-        wgrad(2, g2, z1)
+        w2 = wgrad(2, g2, z1)
         g1 = ops.groupsort_backward(y1, ops.mm(g2, Q2, site="head"), 1)
-        wgrad(1, g1, h)
+        w1 = wgrad(1, g1, h)
         dh = ops.mm(g1, Q1, site="head")
-        for side in sides:
-            cur.wait_stream(side)
-        for dW, db in wg.values():
-            dW.record_stream(cur)
-            db.record_stream(cur)
-        return dh, wg[1][0], wg[1][1], wg[2][0], wg[2][1], wg[3][0], wg[3][1], None
+        (dW3, db3), (dW2, db2), (dW1, db1) = join(w3, w2, w1)
+        return dh, dW1, db1, dW2, db2, dW3, db3, None
 
 
 # the head's output layer and its GroupSort input gradient by fiode_head_out / _backward_gs (<= 16
@@ -636,17 +550,10 @@ def linear_head(mods, h: torch.Tensor):
         return h
     l1, l2, l3 = mods[0::2]
     Q1 = l1.forward_weight()
-    if HEAD_LATE_JOIN:
-        (Q2, j2), (Q3, j3) = l2.forward_weight_unjoined(), l3.forward_weight_unjoined()
-        return _LinearHeadFn.apply(h.contiguous(), Q1, l1.bias, Q2, l2.bias, Q3, l3.bias, (j2, j3))
-    return _LinearHeadFn.apply(h.contiguous(), Q1, l1.bias, l2.forward_weight(), l2.bias,
-                               l3.forward_weight(), l3.bias)
-
-
-# the head joins the 512 -> 512 and 512 -> 10 maps' prefetch right before the layer that reads them,
-# not before its first layer (tools/ab_step.py `head_join_early`)
-HEAD_LATE_JOIN = True
-
+    # the 512 -> 512 and 512 -> 10 maps' prefetch is joined right before the layer that reads them,
+    # not before the first layer
+    (Q2, j2), (Q3, j3) = l2.forward_weight_unjoined(), l3.forward_weight_unjoined()
+    return _LinearHeadFn.apply(h.contiguous(), Q1, l1.bias, Q2, l2.bias, Q3, l3.bias, (j2, j3))
 
 
 class _GroupSortFn(torch.autograd.Function):
@@ -694,15 +601,13 @@ class _SpectralCayleyFn(torch.autograd.Function):
         Q, inv, ws = ops.spectral_cayley_forward(weight.detach(), alpha.detach(), n)
         ctx.save_for_backward(weight, alpha, inv, ws)
         ctx.n = n
-        ctx.step_stream = STEP_STREAM
         return Q
 
     @staticmethod
     def backward(ctx, gQ):
         from . import ops
         weight, alpha, inv, ws = ctx.saved_tensors
-        gw, ga = _run_on_step_stream(SPECTRAL_BWD_ON_MAIN, ctx.step_stream, lambda: ops.spectral_cayley_backward(
-            gQ.contiguous(), weight.detach(), alpha.detach(), ctx.n, inv, ws))
+        gw, ga = ops.spectral_cayley_backward(gQ.contiguous(), weight.detach(), alpha.detach(), ctx.n, inv, ws)
         return gw, ga.reshape(alpha.shape), None
 
 
@@ -793,23 +698,12 @@ class _SpectralConvFn(torch.autograd.Function):
             return gq, gbias
         # the weight / bias gradients beside the input gradient (which alone is on the backward's
         # critical chain), on the side stream of the linear head's, joined before returning
-        side = _head_stream(G.device) if (CONV_WGRAD_SIDE and G.is_cuda and need_x and (need_q or need_b)) else None
-        if side is not None:
-            cur = torch.cuda.current_stream(G.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                gQ, gb = wgrad()
-            G.record_stream(side)
-            X.record_stream(side)
+        # (host tensors, or no input gradient to run beside: no side stream, fork runs them in place)
+        side = _head_stream(G.device) if (G.is_cuda and need_x and (need_q or need_b)) else None
+        branch = fork(side, wgrad, reads=(G, X))
         if need_x:
             gx, _ = ops.sconv_irfft2(_q_h_g(Q, G), n, cin, B, downsample=downsample)
-        if side is not None:
-            cur.wait_stream(side)
-            for t in (gQ, gb):
-                if t is not None:
-                    t.record_stream(cur)
-        else:
-            gQ, gb = wgrad()
+        (gQ, gb), = join(branch)
         return gx, gQ, gb, None, None, None, None, None
 
 
@@ -833,14 +727,10 @@ def _q_h_g(Q, G):
     return ops.cgemm(Q.detach(), G, conj_trans_a=True)
 
 
-CONV_WGRAD_SIDE = os.environ.get("FIODE_CONV_WGRAD_SIDE", "1") != "0"
-
-
-# The conv layers' map-ahead work (map backward, early update, refresh) runs on one stream per layer.
-# (Their weight gradients on those streams instead of the head's side stream -- no join: 110-140 us
-# SLOWER in the step, profiles/r05an -- and one stream shared by all layers were measured and removed.)
-def _conv_map_stream(device) -> "torch.cuda.Stream":
-    return new_stream(device)
+# The conv layers' map-ahead work (map backward, early update, refresh) runs on one stream per layer
+# (streams.StepStreams.conv_stream).  (Their weight gradients on those streams instead of the head's
+# side stream -- no join: 110-140 us SLOWER in the step, profiles/r05an -- and one stream shared by all
+# layers were measured and removed.)
 
 
 class CayleyConv(nn.Conv2d):
@@ -913,7 +803,7 @@ class CayleyConv(nn.Conv2d):
             return False
         from . import ops
         Q, inv, ws = ops.spectral_cayley_forward(self.weight.detach(), self.alpha.detach(), self._n)
-        self._store = {"Q": Q, "inv": inv, "ws": ws, "n": self._n, "stream": _conv_map_stream(self.weight.device)}
+        self._store = {"Q": Q, "inv": inv, "ws": ws, "n": self._n}
         return True
 
     def pipeline_off(self) -> None:
@@ -934,22 +824,18 @@ class CayleyConv(nn.Conv2d):
             return
         if self._n is not None and self._alpha_init:
             n = self._n
-            self._pre = _prefetch(stream, lambda: self.spectral_weight(n, self.weight.device))
+            self._pre = prefetch(stream, lambda: self.spectral_weight(n, self.weight.device))
 
     def _take_spectral(self, n: int, device) -> torch.Tensor:
         st = self._store
         if st is not None and self.training and st["n"] == n and torch.is_grad_enabled():
             # the node's backward (map backward + the store's hook) runs on the layer's own stream
-            side = st["stream"]
-            main = torch.cuda.current_stream(device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                Q = _SpectralCayleyStoredFn.apply(self.weight, self.alpha, n, st)
-            main.wait_stream(side)
+            Q = run_on(current().conv_stream(self),
+                       lambda: _SpectralCayleyStoredFn.apply(self.weight, self.alpha, n, st))
             self._pre = None
             return Q
         if self._pre is not None and self.training and self._n == n:
-            Q = _take(self._pre)
+            Q = take(self._pre)
         else:
             Q = self.spectral_weight(n, device)
         self._pre = None

@@ -27,6 +27,8 @@ from typing import Dict, Iterable, List, Optional, Sequence
 import torch
 import torch.distributed as dist
 
+from .streams import fork, join
+
 
 def world_info():
     """(rank, world, local_rank) from the torch.distributed.run environment (defaults: 0, 1, 0)."""
@@ -211,7 +213,7 @@ class GradAllReducer:
             return
         # the gradient was produced on the hook's current stream (autograd runs a node on its
         # forward's stream, side streams included): the comm stream waits for every one of them
-        st["stream"].wait_stream(torch.cuda.current_stream(st["stream"].device))
+        fork(st["stream"])
         k = self.bucket_of[i]
         p = self.params[i]
         st["fresh"][i] = p.grad
@@ -222,8 +224,8 @@ class GradAllReducer:
     def _launch(self, k):
         st = self._armed
         comm = st["stream"]
-        comm.wait_stream(torch.cuda.current_stream(comm.device))
-        with torch.cuda.stream(comm):
+
+        def launch():
             pairs = []
             for i in self.members[k]:
                 g = st["fresh"][i]
@@ -244,6 +246,7 @@ class GradAllReducer:
             lo, hi = self.buckets[k]
             if st["world"] > 1 or st["force"]:
                 dist.all_reduce(self.flat[lo:hi], group=self.group)
+        fork(comm, launch)
         st["done"][k] = True
 
     def finish(self):
@@ -253,8 +256,7 @@ class GradAllReducer:
         for k in range(len(self.buckets)):
             if not st["done"][k]:
                 self._launch(k)
-        main = torch.cuda.current_stream(self.flat.device)
-        main.wait_stream(st["stream"])
+        join((None, st["stream"]))          # every _launch of this backward is a branch on the comm stream
         if st["world"] > 1 or st["force"]:
             self.flat.div_(st["world"])
         self._armed = None

@@ -17,6 +17,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .cayley import CayleyLinear, cayley_scaled
+from .streams import prefetch, take
 
 
 class LipsLinear(nn.Linear):
@@ -63,15 +64,13 @@ class OrthoClassDynProjectSimplexLips(nn.Module):
     # -- parameters as the kernels take them ---------------------------------------------------
     def prefetch(self, stream) -> None:
         """Compute the next effective_weights() on a side stream (joined at the next call)."""
-        from .cayley import _prefetch
-        self._pre = _prefetch(stream, self._effective_weights)
+        self._pre = prefetch(stream, self._effective_weights)
 
     def effective_weights(self) -> Dict[str, torch.Tensor]:
         pre = getattr(self, "_pre", None)
         if pre is not None:
-            from .cayley import _take
             self._pre = None
-            return _take(pre)
+            return take(pre)
         return self._effective_weights()
 
     def _effective_weights(self) -> Dict[str, torch.Tensor]:

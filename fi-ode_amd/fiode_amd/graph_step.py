@@ -35,19 +35,17 @@ batch shape.  Recapture (construct a new GraphTrainStep) at an epoch boundary.
 """
 from __future__ import annotations
 
-from typing import Optional
-
 import os
+from typing import Optional
 
 import torch
 
-from .streams import distinct, new_stream
+from .streams import StepStreams, distinct, new_stream, run_on
 
 # priority of the stream the step is captured on (its nodes' hardware queue; tools/ab_step.py cap_hi)
 CAPTURE_PRIORITY = 0
 # zeroed GEMM workspace slots reserved per capture (streams made in it that run split-K GEMMs)
 CAPTURE_WS_SLOTS = 24
-
 
 
 # The HIP runtime of this image (ROCm 7.x, torch's libamdhip64) dereferences a null internal stream in
@@ -60,7 +58,6 @@ MIN_HW_QUEUES = 4
 
 
 def _check_runtime_queues() -> None:
-    import os
     q = os.environ.get("GPU_MAX_HW_QUEUES")
     if q is not None and q.strip().isdigit() and int(q) < MIN_HW_QUEUES:
         raise RuntimeError(f"GraphTrainStep: GPU_MAX_HW_QUEUES={q} < {MIN_HW_QUEUES}: this HIP runtime's graph "
@@ -91,7 +88,8 @@ class GraphTrainStep:
         if comm not in ("graph", "eager"):
             raise ValueError(f"comm must be 'graph' or 'eager', got {comm!r}")
         self.comm = comm if multi else "none"
-        self.comm_stream = new_stream(dev) if self.comm == "graph" else None
+        if self.comm == "graph":
+            module.streams.get("comm", dev)
         dyn = module.dyn_fun
         if module.rng_counter is None:
             module.rng_counter = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -102,8 +100,6 @@ class GraphTrainStep:
         self.epoch = module.current_epoch
         self.static_x = x.detach().clone()
         self.static_y = y.detach().clone()
-        if module.rng_counter is None:
-            module.rng_counter = torch.zeros(1, dtype=torch.int64, device=dev)
         self.params = [p for p in module.parameters() if p.requires_grad]
         self.skipped = torch.zeros(1, dtype=torch.int32, device=dev)     # sticky count of guarded skips
         self._guard_ok = guard and hasattr(optimizer, "guard")          # FiodeAdam / FiodeAdamW
@@ -120,9 +116,8 @@ class GraphTrainStep:
         # parameters, the optimizer state and the Philox counter are restored afterwards (in place:
         # the captured graph must see the tensors the warm-up created).
         snap = self._snapshot()
-        side = new_stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
+
+        def warm():
             for it in range(warmup):
                 if it == 0 and multi:
                     reducer.record_order()          # the order the backward finalises the gradients
@@ -131,7 +126,7 @@ class GraphTrainStep:
                     reducer.plan_buckets(reducer.recorded_order(), bucket_bytes)
                 self._between()
                 self.opt.step()
-        torch.cuda.current_stream(dev).wait_stream(side)
+        run_on(new_stream(dev), warm)
         torch.cuda.synchronize(dev)
         self._restore(snap)
         self.skipped.zero_()
@@ -139,6 +134,24 @@ class GraphTrainStep:
 
         if maps_ahead:
             self._maps_ahead_on()
+        # (the warm capture switches torch's AccumulateGrad stream-mismatch warning off for the captures
+        # made here; the caller's setting is back when the constructor ends)
+        warn = torch._C._warn_on_accumulate_grad_stream_mismatch()
+        try:
+            self._capture_all(warm_capture, int(placement_trials))
+        finally:
+            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(warn)
+        if self.reducer is not None and (world > 1 or self.force_comm):
+            views = [self.reducer.flat.data_ptr() <= p.grad.data_ptr() < self.reducer.flat.data_ptr()
+                     + self.reducer.flat.numel() * self.reducer.flat.element_size() for p in self.params]
+            if not all(views):
+                raise RuntimeError("p.grad does not point into the reducer's bucket after capture")
+        self.scalars = module.last_plan["scalars"]
+        # a float lr is a launch argument baked into the captured optimizer step (a tensor lr is
+        # read on the device: LR schedulers may change it between replays)
+        self._float_lrs = [g["lr"] for g in self.opt.param_groups]
+
+    def _capture_all(self, warm_capture: bool, placement_trials: int) -> None:
         # every capture (the first one included) on fresh dedicated streams made in the same order, so
         # the placement trials compare like with like.  warm_capture: the first capture in a process
         # replays ~10 % slower than any later capture of the same step (same kernels, same launch
@@ -171,16 +184,7 @@ class GraphTrainStep:
                 torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
         self.placement_ms = None
         if placement_trials > 1 and self.comm != "eager":
-            self._select_placement(int(placement_trials))
-        if self.reducer is not None and (world > 1 or self.force_comm):
-            views = [self.reducer.flat.data_ptr() <= p.grad.data_ptr() < self.reducer.flat.data_ptr()
-                     + self.reducer.flat.numel() * self.reducer.flat.element_size() for p in self.params]
-            if not all(views):
-                raise RuntimeError("p.grad does not point into the reducer's bucket after capture")
-        self.scalars = module.last_plan["scalars"]
-        # a float lr is a launch argument baked into the captured optimizer step (a tensor lr is
-        # read on the device: LR schedulers may change it between replays)
-        self._float_lrs = [g["lr"] for g in self.opt.param_groups]
+            self._select_placement(placement_trials)
 
     def _select_placement(self, trials: int, reps: int = 12) -> None:
         """Keep the fastest of ``trials`` captures of the same step on different side streams.
@@ -223,25 +227,14 @@ class GraphTrainStep:
                 best = min(best, (time.perf_counter() - t) / reps)
             return best
 
-        stores = [c._store for c in self.piped if getattr(c, "_store", None) is not None]
-
-        def streams():
-            return (getattr(m, "_side_streams", None), getattr(m, "_ode_stream", None),
-                    [st["stream"] for st in stores], getattr(self, "capture_stream", None))
-
-        def use(sv):
-            m._side_streams, m._ode_stream, conv, self.capture_stream = sv
-            for st, cs in zip(stores, conv):
-                st["stream"] = cs
-
         dev = self.static_x.device
-        trials_t = [(clock(), streams())]
+        trials_t = [(clock(), m.streams)]
         for _ in range(trials - 1):
-            # fresh pool streams for the maps' prefetch, the ODE solve, the conv maps computed ahead
-            # and the capture itself
+            # fresh streams for the maps' prefetch, the ODE solve, the conv maps computed ahead and
+            # the capture itself
             self._fresh_streams()
             self._capture()
-            trials_t.append((clock(), streams()))
+            trials_t.append((clock(), m.streams))
         times = [t for t, _ in trials_t]
         import torch.distributed as dist
         if dist.is_initialized() and dist.get_world_size() > 1:
@@ -253,7 +246,7 @@ class GraphTrainStep:
         best = min(range(len(times)), key=lambda i: times[i])
         self.placement_recaptures = 0
         if best != len(trials_t) - 1:
-            use(trials_t[best][1])
+            m.streams = trials_t[best][1]
             self._capture()
             # the recapture on the winner's streams replays like its trial -- but once a bench read
             # 1.322 ms after a 1.218 ms trial (profiles/r06/warm_capture.json): check it and capture
@@ -279,33 +272,21 @@ class GraphTrainStep:
         self.placement_pick = best
 
     def _fresh_streams(self) -> None:
-        """New dedicated streams (fiode_amd.streams) for the module's map prefetch and ODE solve
-        (made at their first use in the capture), the conv maps computed ahead and the capture."""
+        """A new owner (streams.StepStreams) for the module: new dedicated streams for the conv maps
+        computed ahead and the capture, made here, and for the map prefetch and the ODE solve, made at
+        their first use in the capture.  The comm and weight-tap streams stay the same ones."""
         m, dev = self.module, self.static_x.device
-        m._side_streams = m._ode_stream = None
+        old, m.streams = m.streams, StepStreams()
+        m.streams.comm, m.streams.wtap = old.comm, old.wtap
         for c in self.piped:
-            if getattr(c, "_store", None) is not None:
-                c._store["stream"] = new_stream(dev)
-        self.capture_stream = new_stream(dev, priority=CAPTURE_PRIORITY)
-
-    def role_streams(self) -> list:
-        """Every stream a capture of this step forks work to: the capture stream, the module's map
-        prefetch / ODE / weight-tap streams, the conv maps' streams, the comm stream and the
-        module-level head stream."""
-        from . import cayley as CY
-        m = self.module
-        out = [getattr(self, "capture_stream", None), getattr(self, "comm_stream", None),
-               getattr(m, "_ode_stream", None), getattr(m, "_wtap_stream", None)]
-        out += list(getattr(m, "_side_streams", None) or [])
-        out += [c._store["stream"] for c in self.piped if getattr(c, "_store", None) is not None]
-        out += list(CY._HEAD_STREAMS.values())
-        return out
+            m.streams.conv_stream(c)
+        m.streams.get("capture", dev, priority=CAPTURE_PRIORITY)
 
     def _capture(self):
         # two roles on one HIP stream can make a stream that joined the capture wait on an event it
         # recorded itself, which this ROCm runtime answers with a host SIGSEGV in hipStreamEndCapture
         # (streams.py); the product's streams are dedicated, so this only trips on a caller's own
-        if not distinct(self.role_streams()):
+        if not distinct(self.module.streams.all()):
             raise RuntimeError("GraphTrainStep: two roles of the captured step share one HIP stream "
                                "(use fiode_amd.streams.new_stream for side streams, not the torch pool)")
         self.one_graph = self.single or self.comm == "graph"
@@ -317,7 +298,7 @@ class GraphTrainStep:
         # during our capture; in the default "global" mode such a call from ANOTHER thread aborts it
         # ("operation not permitted when stream is capturing" -> the watchdog terminates the process)
         self.g_fb = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_fb, stream=getattr(self, "capture_stream", None),
+        with torch.cuda.graph(self.g_fb, stream=self.module.streams.capture,
                               capture_error_mode="thread_local"):
             self.loss = self._fwd_bwd()
             if self.one_graph:
@@ -326,7 +307,7 @@ class GraphTrainStep:
         self.g_opt = None
         if not self.one_graph:
             self.g_opt = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.g_opt, stream=getattr(self, "capture_stream", None),
+            with torch.cuda.graph(self.g_opt, stream=self.module.streams.capture,
                                   capture_error_mode="thread_local"):
                 self.opt.step()
                 self._refresh_late()
@@ -430,7 +411,7 @@ class GraphTrainStep:
             p.grad = None
         overlap = self.comm == "graph" and bucket_plan
         if overlap:
-            self.reducer.arm(self.world, self.comm_stream, force=self.force_comm)
+            self.reducer.arm(self.world, m.streams.comm, force=self.force_comm)
         loss = m.compute_loss(self.static_x, self.static_y, self.static_x.shape[0], self.act)
         self._arm_guard(loss)
         loss.backward(self._unit_grad(loss))

@@ -13,7 +13,6 @@ validation_step, configure_optimizers, log, current_epoch, global_step).
 """
 from __future__ import annotations
 
-import os
 from typing import Dict, Optional
 
 import numpy as np
@@ -28,7 +27,7 @@ from .models import IVP, DefaultOutputFun
 from .odeint import make_solver_params
 from .optim import FiodeAdam, FiodeAdamW
 from .sampling import CompositeSampler, CompositeSamplerScheduler, TrajectorySampler
-from .streams import new_stream
+from .streams import StepStreams, current, prefetch, run_on, take
 
 
 class LyapunovLossFn(torch.autograd.Function):
@@ -69,27 +68,21 @@ class ODETrainFn(torch.autograd.Function):
         plan["stats"] = stats
         plan["status_word"] = ops.odetrain_status_word(ws, plan["cfg"])
         ctx.plan, ctx.w, ctx.xf, ctx.ws = plan, w, xf, ws
-        from . import cayley as _cy
-        ctx.step_stream = _cy.STEP_STREAM
+        ctx.step_stream = current().step
         return y
 
     @staticmethod
     def backward(ctx, g_y):
         # The forward ran on a side stream beside the fan-out kernels; the backward has nothing to
         # overlap with (the backbone backward needs its dL/dx_feat), so it runs on the step stream
-        # that produces g_y and consumes the gradients (ODE_BWD_ON_MAIN: no cross-queue hops).
-        from . import cayley as _cy
-
+        # that produces g_y and consumes the gradients (no cross-queue hops).
         def run():
             grads, _ = ops.odetrain_backward(g_y.contiguous(), ctx.xf, ctx.w, ctx.plan["dyn"], ctx.plan["cfg"],
                                              ctx.ws)
             return tuple(grads[k] for k in ("x_feat", "Q1", "b1", "Qx", "bx", "Q2", "b2", "Q3", "b3"))
-        out = _cy._run_on_step_stream(ODE_BWD_ON_MAIN, ctx.step_stream, run)
+        out = run_on(ctx.step_stream, run)
         ctx.ws = None
         return tuple(out) + (None, None)
-
-
-ODE_BWD_ON_MAIN = True
 
 
 class ODENllFn(torch.autograd.Function):
@@ -148,7 +141,7 @@ UNIT_GRAD = "_fiode_unit_grad"
 # The dynamics weights' gradient of the training loss as its own autograd node on a side stream
 # (_DynWeightTapFn): LyapODELossFn's backward then ends with dL/dx_feat, which alone the backbone's
 # backward waits for
-DYN_WGRAD_SIDE = os.environ.get("FIODE_DYN_WGRAD_SIDE", "1") != "0"
+DYN_WGRAD_SIDE = True        # False: inside LyapODELossFn's backward (the tests' reference)
 
 
 _ONES: dict = {}
@@ -195,7 +188,6 @@ class LyapODELossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x_feat, x_ode, Q1, b1, Qx, bx, Q2, b2, Q3, b3, h0, y, plan: dict, oplan: dict, p: float,
                 ode_stream, box=None, tok=None):
-        from .cayley import _prefetch, _take
         w = {"Q1": Q1, "b1": b1, "Qx": Qx, "bx": bx, "Q2": Q2, "b2": b2, "Q3": Q3, "b3": b3}
         w = {k: v.detach().contiguous() for k, v in w.items()}
         xf = x_feat.detach().float().contiguous()
@@ -204,7 +196,7 @@ class LyapODELossFn(torch.autograd.Function):
         def solve():
             return ops.odetrain_forward(xo, h0.detach().float().contiguous(), w, oplan["dyn"], oplan["cfg"],
                                         masks=oplan.get("masks"), offset_dev=oplan.get("offset_dev"))
-        pre = _prefetch(ode_stream, solve) if ode_stream is not None else None
+        pre = prefetch(ode_stream, solve) if ode_stream is not None else None
         res = None if pre is not None else solve()
         sc, grads, dbg = ops.lyap_step(
             xf, y, w, plan["dyn"], sample_size=plan["S"], n_uniform=plan["S1"],
@@ -219,11 +211,7 @@ class LyapODELossFn(torch.autograd.Function):
         # backward (on the captured step's critical path)
         ctx.lyap_unit = torch._foreach_mul(ctx.lyap, 1.0 - float(p))
         if pre is not None:
-            main = torch.cuda.current_stream(xf.device)
-            main.wait_event(pre[1])
-            for t in pre[0]:
-                t.record_stream(main)
-            res = pre[0]
+            res = take(pre)
         y_hat, stats, ws = res
         oplan["stats"] = stats
         oplan["status_word"] = ops.odetrain_status_word(ws, oplan["cfg"])
@@ -307,10 +295,6 @@ class DecisionBoundary(nn.Module):
         return torch.log(v) if self.log_mode else v
 
 
-# the solve's h0 kept contiguous between steps (tools/ab_step.py `h0_copy`: copied every step)
-H0_CACHE = True
-
-
 class UniformInitFun(nn.Module):
     """dynamics/init_coordinates.py:38-44: h0 = 1/C, static = param_map(x)."""
 
@@ -380,7 +364,7 @@ class LyapunovLearning(nn.Module):
         # the configs[1] loss as one autograd node (LyapODELossFn); False: three nodes (the Lyapunov
         # step, the solve, the mix) as in round 1
         self.fused_ode_loss = True
-        self._side_streams = None
+        self.streams = StepStreams()    # the side streams of this module's step (GraphTrainStep: one per capture)
         # capture points of the Cayley maps' prefetch (_prefetch_weights): the 4096 -> 512 map right
         # after the input kernels, the other maps after conv layer 2 (None: all of them at the input)
         self._prefetch_late_at = 2
@@ -548,54 +532,39 @@ class LyapunovLearning(nn.Module):
         skip their launch here).  Measured alternatives
         (deferral past conv layers, one stream per map, one chain for all
         linear maps, one batched inverse for both 512 x 512 systems) were all slower or equal."""
-        if not getattr(self, "_in_input_hook", False):
-            bb = self.init_coordinates.param_map
-            target = bb[-1] if isinstance(bb, torch.nn.Sequential) else bb
+        bb = self.init_coordinates.param_map
+        target = bb[-1] if isinstance(bb, torch.nn.Sequential) else bb
+        late = self._prefetch_late_at       # the maps after the first: after this conv layer
+        last = -1 if late is None else max(-1, late)
 
-            at = getattr(self, "_prefetch_at", -1)      # tools/ab_step.py probes later capture points
+        def hook(i, _t=target):
+            if i == -1 or i == late:
+                self._launch_prefetch(device, None if late is None else ("first" if i == -1 else "rest"))
+            if i >= last:
+                _t.after_conv_hook = None
+        target.after_conv_hook = hook
 
-            late = getattr(self, "_prefetch_late_at", None)   # the maps after the first: after this conv layer
-
-            last = max(x for x in (at, late) if x is not None)
-
-            def hook(i, _t=target, _at=at):
-                if i == _at or (late is not None and i == late):
-                    self._in_input_hook = True
-                    self._prefetch_part = None if late is None else ("first" if i == _at else "rest")
-                    try:
-                        self._prefetch_weights(device)
-                    finally:
-                        self._in_input_hook = False
-                        self._prefetch_part = None
-                if i >= last:
-                    _t.after_conv_hook = None
-            target.after_conv_hook = hook
-            return
-        if self._side_streams is None:
-            self._side_streams = [new_stream(device) for _ in range(4)]
-        s = self._side_streams
+    def _launch_prefetch(self, device, part):
+        """The launches of _prefetch_weights: all of them (``part`` None), the 4096 -> 512 map and the
+        conv maps ('first'), or the other linear maps and the dynamics' ('rest')."""
+        s = self.streams.map_streams(device)
         convs, lins = [], []
         for m in self.init_coordinates.modules():
             if hasattr(m, "prefetch") and m is not self.dyn_fun:
                 (convs if hasattr(m, "spectral_weight") else lins).append(m)
-        order = getattr(self, "_map_streams", (1, 2, 3, 3))   # side stream of each linear map, then dyn's
-        part = getattr(self, "_prefetch_part", None)
-        nfirst = getattr(self, "_prefetch_first_lins", 1)       # linear maps in the first stage
-        dyn_first = getattr(self, "_prefetch_dyn_first", False)
-        for i, l in enumerate(lins):
-            if part is None or (part == "first") == (i < nfirst):
-                l.prefetch(s[order[min(i, 2)]])
-        if part is None or (part == "first") == dyn_first:
-            self.dyn_fun.prefetch(s[order[3]])
+        for i, l in enumerate(lins):             # linear map i on side stream 1, 2, 3, 3, ...
+            if part is None or (part == "first") == (i < 1):
+                l.prefetch(s[min(i, 2) + 1])
+        if part != "first":
+            self.dyn_fun.prefetch(s[3])
         if part != "rest":             # (before conv layer 0: a map prefetched later would go unused)
             for c in convs:
                 c.prefetch(s[0])
 
     def compute_loss(self, x, y, batch_size=None, act="relu", h=None, masks=None, debug=False):
         """pl_modules.py:390-502 with the per-sample graph fused (LyapunovLossFn)."""
-        from . import cayley as _cy
         step_stream = torch.cuda.current_stream(x.device) if x.is_cuda else None
-        with _cy.step_stream_scope(step_stream):
+        with self.streams.scope(step_stream):
             return self._compute_loss(x, y, h=h, masks=masks, debug=debug)
 
     def _compute_loss(self, x, y, h=None, masks=None, debug=False):
@@ -620,7 +589,7 @@ class LyapunovLearning(nn.Module):
                 # default reuses the features (the backbone is deterministic: same value, one pass)
                 feat_ode, _ = self.init_coordinates(x, self.dyn_fun)
             y_hat = self._ode_launch(feat_ode.float(), w)
-            if isinstance(y_hat, tuple) and self.lyap_after_ode:
+            if isinstance(y_hat, tuple) and y_hat[1] is not None and self.lyap_after_ode:
                 # k_ot_fwd is a persistent latency chain whose 8 workgroups exchange QP exit masks:
                 # dispatched beside the fan-out kernels, some of its workgroups wait for CUs while the
                 # resident ones spin.  Ordering the fan-out after the solve's forward lets the solve
@@ -710,12 +679,13 @@ class LyapunovLearning(nn.Module):
         w = {k: (v.view_as(v) if v.is_leaf and v.requires_grad else v) for k, v in w.items()}
         args = (static_state, w["Q1"], w["b1"], w["Qx"], w["bx"], w["Q2"], w["b2"], w["Q3"], w["b3"], h0, plan)
         self.last_ode_plan = plan
-        if static_state.is_cuda and self.parallel_cayley and getattr(self, "ode_side_stream", True):
-            from .cayley import _prefetch
-            if getattr(self, "_ode_stream", None) is None:
-                self._ode_stream = new_stream(static_state.device, priority=getattr(self, "_ode_prio", -1))
-            return _prefetch(self._ode_stream, lambda: ODETrainFn.apply(*args))
+        if static_state.is_cuda and self.parallel_cayley:
+            return prefetch(self._ode_stream(static_state.device), lambda: ODETrainFn.apply(*args))
         return ODETrainFn.apply(*args)
+
+    def _ode_stream(self, device):
+        """The solve's side stream, at high priority."""
+        return self.streams.get("ode", device, priority=-1)
 
     def _h0(self, B: int) -> torch.Tensor:
         """The solve's initial state h0 = 1/C for every row (init_coordinates.py:38-44) as the
@@ -725,10 +695,10 @@ class LyapunovLearning(nn.Module):
         h0_0 = self.init_coordinates.h0_0
         key = (B, h0_0.device, h0_0.data_ptr(), h0_0._version)
         c = getattr(self, "_h0_cache", None)
-        if H0_CACHE and c is not None and c[0] == key:
+        if c is not None and c[0] == key:
             return c[1]
         h0 = h0_0[None].expand(B, -1).float().contiguous()
-        if H0_CACHE and not (h0.is_cuda and torch.cuda.is_current_stream_capturing()):
+        if not (h0.is_cuda and torch.cuda.is_current_stream_capturing()):
             self._h0_cache = (key, h0)
         return h0
 
@@ -742,22 +712,13 @@ class LyapunovLearning(nn.Module):
         h0 = self._h0(static_state.shape[0])
         oplan = self.ode_plan(static_state.shape[0])
         self.last_ode_plan = oplan
-        stream = None
-        if self.parallel_cayley and getattr(self, "ode_side_stream", True):
-            if getattr(self, "_ode_stream", None) is None:
-                self._ode_stream = new_stream(static_state.device, priority=getattr(self, "_ode_prio", -1))
-            stream = self._ode_stream
+        stream = self._ode_stream(static_state.device) if self.parallel_cayley else None
         p = min(0.98, (self.current_epoch - self.train_ode_epoch) / 50.0)
         keys = ("Q1", "b1", "Qx", "bx", "Q2", "b2", "Q3", "b3")
         if DYN_WGRAD_SIDE and static_state.is_cuda and torch.is_grad_enabled():
             box = {}
-            if getattr(self, "_wtap_stream", None) is None:
-                self._wtap_stream = new_stream(static_state.device)
-            side, main = self._wtap_stream, torch.cuda.current_stream(static_state.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                tok = _DynWeightTapFn.apply(box, *[w[k] for k in keys])
-            main.wait_stream(side)
+            tok = run_on(self.streams.get("wtap", static_state.device),
+                         lambda: _DynWeightTapFn.apply(box, *[w[k] for k in keys]))
             wd = [w[k].detach() for k in keys]
             total = LyapODELossFn.apply(static_state, x_ode, *wd, h0, y, plan, oplan, p, stream, box, tok)
         else:
@@ -773,8 +734,7 @@ class LyapunovLearning(nn.Module):
     def _ode_loss(self, loss, y_hat, y):
         """pl_modules.py:494-500: loss * (1 - p) + nll(log y_hat) * p."""
         if isinstance(y_hat, tuple):
-            from .cayley import _take
-            y_hat = _take(y_hat)
+            y_hat = take(y_hat)
         p = min(0.98, (self.current_epoch - self.train_ode_epoch) / 50.0)
         if (self.simplex and y_hat.is_cuda and y.dtype == torch.int64 and y_hat.dim() == 2 and y_hat.shape[1] == 10
                 and loss.is_cuda):

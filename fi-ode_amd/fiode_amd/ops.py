@@ -57,10 +57,6 @@ def _need(t: torch.Tensor, name: str, shape, dtype, dev) -> torch.Tensor:
     return t.contiguous()
 
 
-# tools/ab_step.py `ws_fill`: zeroed workspaces made inside a capture by a captured fill (before r06)
-WS_FILL_IN_CAPTURE = False
-
-
 class _Workspace:
     _cache: Dict[tuple, torch.Tensor] = {}
     _arena: Dict[int, list] = {}          # device -> [buffer, slot bytes, next slot]
@@ -89,7 +85,7 @@ class _Workspace:
                 cls._retired.append(buf)
             n = max(int(nbytes), 256)
             ar = cls._arena.get(dev.index)
-            if (zero and not WS_FILL_IN_CAPTURE and ar is not None and ar[1] >= n and
+            if (zero and ar is not None and ar[1] >= n and
                     (ar[2] + 1) * ar[1] <= ar[0].numel() and torch.cuda.is_current_stream_capturing()):
                 buf = ar[0][ar[2] * ar[1]:(ar[2] + 1) * ar[1]]
                 ar[2] += 1

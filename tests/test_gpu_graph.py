@@ -13,8 +13,8 @@ def _dev():
 
 
 @pytest.mark.filterwarnings("error:.*AccumulateGrad node's stream.*:UserWarning")
-@pytest.mark.parametrize("train_ode", [False, True])
-def test_graph_replay_matches_eager_step(train_ode):
+@pytest.mark.parametrize("train_ode,warm_capture", [(False, False), (False, True), (True, False), (True, True)])
+def test_graph_replay_matches_eager_step(train_ode, warm_capture):
     import bench
     from fiode_amd.graph_step import GraphTrainStep
     dev = _dev()
@@ -23,9 +23,9 @@ def test_graph_replay_matches_eager_step(train_ode):
     x = torch.rand(32, 3, 32, 32, generator=g).to(dev)
     y = torch.randint(0, 10, (32,), generator=g).to(dev)
     opt = mod.configure_optimizers(capturable=True)[0][0]
-    # one capture, so that the AccumulateGrad-stream check above holds (the default warm capture
-    # binds the parameters' accumulators to its own stream on purpose: graph_step.py)
-    gs = GraphTrainStep(mod, opt, x, y, warmup=2, warm_capture=False)
+    warn = torch._C._warn_on_accumulate_grad_stream_mismatch()
+    gs = GraphTrainStep(mod, opt, x, y, warmup=2, warm_capture=warm_capture)
+    assert torch._C._warn_on_accumulate_grad_stream_mismatch() == warn     # (switched off only inside)
     twin = bench.build_module(dev, seed=1, train_ode=train_ode)          # same parameters / counter as before the replay
     twin.load_state_dict(mod.state_dict())
     twin.rng_counter = mod.rng_counter.clone()
@@ -262,7 +262,7 @@ def test_placement_trials_use_distinct_dedicated_streams():
     torch pool streams that could alias another role's stream: after the trials every role stream of
     the kept capture is a distinct HIP stream, and the capture-time check refuses an aliased one."""
     import bench
-    from fiode_amd import cayley as CY, streams
+    from fiode_amd import streams
     from fiode_amd.graph_step import GraphTrainStep
     dev = _dev()
     g = torch.Generator(device="cpu").manual_seed(5)
@@ -273,13 +273,44 @@ def test_placement_trials_use_distinct_dedicated_streams():
     from fiode_amd import ops
     fills = ops._Workspace.fills_in_capture
     gs = GraphTrainStep(mod, opt, x, y, warmup=2, placement_trials=4)
-    roles = [s for s in gs.role_streams() if s is not None]
+    roles = mod.streams.all()
     assert len(roles) >= 8 and streams.distinct(roles)
     # every zeroed GEMM workspace of the 5 captures came from a reserved arena (no captured fill)
     assert ops._Workspace.fills_in_capture == fills
     gs.step()
     torch.cuda.synchronize()
-    mod._wtap_stream = CY._head_stream(dev)          # two roles on one stream: refused before capturing
+    mod.streams.wtap = mod.streams.ode               # two roles on one stream: refused before capturing
     with pytest.raises(RuntimeError, match="share one HIP stream"):
         gs._capture()
     gs.close()
+
+
+# priorities of the streams GraphTrainStep(train_ode=True, warmup=2, placement_trials=4) makes, in
+# creation order, as recorded from the commit before streams.StepStreams: the warm-up stream, the
+# eager warm-up's 4 map-prefetch, ODE (-1) and weight-tap streams and the head's 3 shared ones, then 4
+# conv-map, the capture, 4 map-prefetch and the ODE stream for each of the 5 captures (one dropped,
+# one kept, three more trials).  Left out of that record: the 4 conv-map streams pipeline_on used to
+# make between the warm-up and the first capture, which no capture or replay ever ran on.
+_WARMUP_TRACE = [0, 0, 0, 0, 0, -1, 0, 0, 0, 0]
+_CAPTURE_TRACE = [0, 0, 0, 0, 0, 0, 0, 0, 0, -1]
+STREAM_TRACE = _WARMUP_TRACE + 5 * _CAPTURE_TRACE
+
+
+def test_stream_creation_trace(monkeypatch):
+    """Which hardware queue a stream gets is fixed when it is made, so the step keeps its placement
+    only if the constructor makes the same streams, with the same priorities, in the same order."""
+    import bench
+    from fiode_amd import streams
+    from fiode_amd.graph_step import GraphTrainStep
+    dev = _dev()
+    monkeypatch.setattr(streams, "_SHARED", {})      # as in a fresh process: the shared streams not made yet
+    g = torch.Generator(device="cpu").manual_seed(5)
+    x = torch.rand(32, 3, 32, 32, generator=g).to(dev)
+    y = torch.randint(0, 10, (32,), generator=g).to(dev)
+    mod = bench.build_module(dev, seed=0, train_ode=True)
+    opt = mod.configure_optimizers(capturable=True)[0][0]
+    n0 = len(streams._MADE)
+    gs = GraphTrainStep(mod, opt, x, y, warmup=2, placement_trials=4)
+    trace = [prio for _, _, prio in streams._MADE[n0:]]
+    gs.close()
+    assert trace == STREAM_TRACE

@@ -62,21 +62,7 @@ def unfused_loss(m):
     m.fused_ode_loss = False
 
 
-def pf_conv0(m):
-    m._prefetch_at = 0        # map prefetch captured after conv layer 0 instead of before it
-
-
-def pf_conv1(m):
-    m._prefetch_at = 1
-
-
 RESTORE = []      # module-level switches a variant flips for its own capture only
-
-
-def dense_bwd_side(m):
-    from fiode_amd import cayley as CY
-    CY.DENSE_BWD_ON_MAIN = False  # each dense map's backward on its forward's (prefetch) stream
-    RESTORE.append(lambda: setattr(CY, "DENSE_BWD_ON_MAIN", True))
 
 
 def lib_gmn(m):
@@ -85,16 +71,8 @@ def lib_gmn(m):
     RESTORE.append(lambda: setattr(CY, "DENSE_GEMM", True))
 
 
-
-
-def ode_on_main(m):
-    m.ode_side_stream = False
-
-
 def seed1000(m):
     m.seed = 1000
-
-
 
 
 def old_seed(m):
@@ -144,35 +122,6 @@ def late_scale(m):
     RESTORE.append(lambda: setattr(LY.LyapODELossFn, "backward", staticmethod(nb)))
 
 
-def ms_213(m):
-    m._map_streams = (2, 1, 3, 3)       # the 4096 -> 512 map on side stream 2, 512 -> 512 on 1
-
-
-def ms_321(m):
-    m._map_streams = (3, 2, 1, 1)
-
-
-def ms_3222(m):
-    m._map_streams = (3, 2, 2, 2)
-
-
-def ms_0(m):
-    m._map_streams = (0, 2, 3, 3)       # the 4096 -> 512 map on the conv maps' stream
-
-
-def first_ab(m):
-    m._prefetch_first_lins = 2  # the 4096 -> 512 and 512 -> 512 maps before the conv stack
-
-
-def first_dyn(m):
-    m._prefetch_dyn_first = True   # the dynamics' maps before the conv stack too
-
-
-def late2_first_ab(m):
-    m._prefetch_first_lins = 2
-    m._prefetch_dyn_first = True
-
-
 def all_first(m):
     m._prefetch_late_at = None  # every map prefetched right after the input kernels (before r04bc)
 
@@ -199,34 +148,10 @@ def head_autograd(m):
     RESTORE.append(lambda: setattr(CY, "HEAD_WGRAD_SIDE", True))
 
 
-def conv_wgrad_main(m):
-    from fiode_amd import cayley as CY
-    CY.CONV_WGRAD_SIDE = False    # the conv layers' weight / bias gradients after the input gradient, one stream
-    RESTORE.append(lambda: setattr(CY, "CONV_WGRAD_SIDE", True))
-
-
-
-
-
-
-
-
 def cap_hi(m):
     from fiode_amd import graph_step as GS
     GS.CAPTURE_PRIORITY = -1          # the step captured on a high-priority stream
     RESTORE.append(lambda: setattr(GS, "CAPTURE_PRIORITY", 0))
-
-
-def ode_lo(m):
-    m._ode_prio = 0                   # the train_ode solve's stream at normal priority
-
-
-
-
-
-
-
-
 
 
 def norm_unfused(m):
@@ -235,8 +160,6 @@ def norm_unfused(m):
 
 def nchw_last_off(m):
     m.init_coordinates.param_map[1].nchw_last = False    # the flatten's permute copies (before r05bo)
-
-
 
 
 def qx_off(m):
@@ -265,17 +188,6 @@ def _lib_site(site):
     return f
 
 
-def head_join_early(m):
-    from fiode_amd import cayley as CY
-    CY.HEAD_LATE_JOIN = False     # the head joins all three maps before its first layer (before r06)
-    RESTORE.append(lambda: setattr(CY, "HEAD_LATE_JOIN", True))
-
-
-def all_first_side(m):
-    all_first(m)                  # every map prefetched at the step start: their nodes rank last ...
-    dense_bwd_side(m)             # ... and each dense map's backward on its own prefetch stream
-
-
 def _prio(mask):
     def v(m):
         import ctypes
@@ -289,18 +201,6 @@ def _prio(mask):
 
 def no_warm(m):
     m._no_warm = True
-
-
-def head_wg1(m):
-    from fiode_amd import cayley as CY
-    CY.HEAD_WGRAD_STREAMS = 1     # the head's three weight gradients in sequence on one stream (before r06)
-    RESTORE.append(lambda: setattr(CY, "HEAD_WGRAD_STREAMS", 3))
-
-
-def h0_copy(m):
-    from fiode_amd import lyapunov as LY
-    LY.H0_CACHE = False
-    RESTORE.append(lambda: setattr(LY, "H0_CACHE", True))
 
 
 def own_gemm(m):
@@ -334,12 +234,6 @@ def dyn_wgrad_main(m):
     RESTORE.append(lambda: setattr(LY, "DYN_WGRAD_SIDE", True))
 
 
-def ws_fill(m):
-    from fiode_amd import ops as OPS
-    OPS.WS_FILL_IN_CAPTURE = True     # GEMM workspaces made in the capture zeroed by a captured fill
-    RESTORE.append(lambda: setattr(OPS, "WS_FILL_IN_CAPTURE", False))
-
-
 def no_pair(m):
     from fiode_amd import ops as OPS
     OPS.MM_PAIR = False           # the dense maps' backward A and P2 as two launches (before r06)
@@ -349,15 +243,15 @@ def no_pair(m):
 # variants of paths removed from the product after their A/B (the conv weight gradients on the map
 # streams, fiode_cgemm for w G X^H, the library for thin / Q^H G products, h0 repeat, the pre-solve
 # zero fill, one shared conv map stream) are kept only as records in DESIGN.md section 11
-ALL = {"default": default, "ws_fill": ws_fill, "no_pair": no_pair, "lib_gemm": lib_gemm, "wgrad_lib": wgrad_lib, "r05_gemms": r05_gemms, "lib_dense_fwd": _lib_site("dense_fwd"),
-       "lib_dense_bwd": _lib_site("dense_bwd"), "lib_head": _lib_site("head"), "lib3": lib3, "own_gemm": own_gemm, "h0_copy": h0_copy, "head_wg1": head_wg1, "no_warm": no_warm, "prio_otf": _prio(1), "prio_otb": _prio(2), "prio_small": _prio(4),
+ALL = {"default": default, "no_pair": no_pair, "lib_gemm": lib_gemm, "wgrad_lib": wgrad_lib, "r05_gemms": r05_gemms, "lib_dense_fwd": _lib_site("dense_fwd"),
+       "lib_dense_bwd": _lib_site("dense_bwd"), "lib_head": _lib_site("head"), "lib3": lib3, "own_gemm": own_gemm, "no_warm": no_warm, "prio_otf": _prio(1), "prio_otb": _prio(2), "prio_small": _prio(4),
        "prio_pinv": _prio(8), "prio_all": _prio(15), "prio_ot": _prio(3),
-       "prio_none": _prio(0), "all_first_side": all_first_side, "head_join_early": head_join_early, "head_autograd": head_autograd, "conv_wgrad_main": conv_wgrad_main,
-       "cap_hi": cap_hi, "ode_lo": ode_lo, "norm_unfused": norm_unfused, "nchw_last_off": nchw_last_off, "dyn_wgrad_main": dyn_wgrad_main, "qx_off": qx_off, "head_out_lib": head_out_lib, "all_first": all_first, "first_ab": first_ab, "first_dyn": first_dyn,
-       "late2_first_ab": late2_first_ab, "late0": late0, "late1": late1, "late2": late2, "late3": late3, "late3b": late3,
-       "default_b": default, "ms_213": ms_213, "ms_321": ms_321, "ms_3222": ms_3222, "ms_0": ms_0, "torch_norm": torch_norm, "late_scale": late_scale, "after_ode": after_ode, "no_ahead": no_ahead, "torch_adam": torch_adam,
-       "unfused_loss": unfused_loss, "ode_on_main": ode_on_main, "seed1000": seed1000, "pf_conv0": pf_conv0,
-       "pf_conv1": pf_conv1, "dense_bwd_side": dense_bwd_side, "lib_gmn": lib_gmn, "old_seed": old_seed}
+       "prio_none": _prio(0), "head_autograd": head_autograd,
+       "cap_hi": cap_hi, "norm_unfused": norm_unfused, "nchw_last_off": nchw_last_off, "dyn_wgrad_main": dyn_wgrad_main, "qx_off": qx_off, "head_out_lib": head_out_lib, "all_first": all_first,
+       "late0": late0, "late1": late1, "late2": late2, "late3": late3, "late3b": late3,
+       "default_b": default, "torch_norm": torch_norm, "late_scale": late_scale, "after_ode": after_ode, "no_ahead": no_ahead, "torch_adam": torch_adam,
+       "unfused_loss": unfused_loss, "seed1000": seed1000,
+       "lib_gmn": lib_gmn, "old_seed": old_seed}
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 6
 names = sys.argv[2].split(",") if len(sys.argv) > 2 else ["default", "no_ahead"]
 VARIANTS = {k: ALL[k] for k in names}

@@ -2,9 +2,8 @@
 few times, for a rocprofv3 --kernel-trace --stats breakdown of where its ~7.4 ms go.  Prints the
 replay time from HIP events.  (tools; not a test)
 
-usage: rocprofv3 --kernel-trace --stats -d <dir> -o run -- python tools/probes/large_step_trace.py [replays] [modes]
-modes (comma list, default "side"): side = the solve on its own stream beside the fan-out (the
-product), serial = the solve on the step's stream (ode_side_stream False); alternated 3 rounds.
+usage: rocprofv3 --kernel-trace --stats -d <dir> -o run -- python tools/probes/large_step_trace.py [replays]
+Three rounds of ``replays`` steps.
 """
 import json
 import os
@@ -19,14 +18,13 @@ from fiode_amd.graph_step import GraphTrainStep  # noqa: E402
 
 dev = torch.device("cuda:0")
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-modes = (sys.argv[2] if len(sys.argv) > 2 else "side").split(",")
+modes = ["side"]          # the solve on its own stream beside the fan-out (the product)
 g = torch.Generator(device="cpu").manual_seed(1234)
 x = torch.rand(1024, 3, 32, 32, generator=g).to(dev)
 y = torch.randint(0, 10, (1024,), generator=g).to(dev)
 steps = {}
 for mode in modes:
     mod = bench.build_module(dev, seed=0, train_ode=True, solver="dopri5", h_sample=1024)
-    mod.ode_side_stream = mode != "serial"
     opt = mod.configure_optimizers(capturable=True)[0][0]
     steps[mode] = GraphTrainStep(mod, opt, x, y, placement_trials=1)
 times = {m: [] for m in modes}

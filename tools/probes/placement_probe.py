@@ -6,7 +6,7 @@ The same module and batch captured several ways, each timed over the same replay
   first       GraphTrainStep as bench.py builds it
   recapture   gs._capture() again: every stream object the same
   new_gs      a second GraphTrainStep on the module (side / ODE streams kept; conv map streams new)
-  fresh_k     the module's side and ODE streams dropped first (new pool streams), k = 0..3
+  fresh_k     the module's stream owner replaced first (all streams new), k = 0..3
 """
 import json
 import pathlib
@@ -19,6 +19,7 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from fiode_amd.graph_step import GraphTrainStep  # noqa: E402
+from fiode_amd.streams import StepStreams  # noqa: E402
 
 dev = torch.device("cuda:0")
 torch.cuda.set_device(dev)
@@ -55,8 +56,7 @@ gs = GraphTrainStep(mod, opt, x, y)
 res["new_gs"] = timed(gs)
 for k in range(4):
     gs.close()
-    mod._side_streams = None
-    mod._ode_stream = None
+    mod.streams = StepStreams()
     gs = GraphTrainStep(mod, opt, x, y)
     res[f"fresh_{k}"] = timed(gs)
     gs._capture()
