@@ -169,6 +169,7 @@ __device__ __forceinline__ void and_by_batch(const CertArgs& a, int batch, bool 
 // them).  A wave takes two consecutive 32-row tiles: both MLPs (dropout off: plain relu), then one
 // QP per lane -- lanes 0..31 the first tile's rows, 32..63 the second's (a 32x32 accumulator tile
 // leaves each row's outputs on both lane halves, so a wave per tile ran every row's QP twice).
+template <Act A>
 __global__ __launch_bounds__(256, 2) void k_cert_fwd(CertArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Q2s = smem;
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void k_cert_fwd(CertArgs a) {
       float ht[C];
       eta_row(a, tab, rrt, ht);
       f32x16 z1[4], z2[4];
-      const f32x16 z3 = mlp_tile<false>(Q2s, Q3s, q1, a.u, a.b2, a.b3, ht, kw, kw, 1.0f, col, half, z1, z2);
+      const f32x16 z3 = mlp_tile<false, A>(Q2s, Q3s, q1, a.u, a.b2, a.b3, ht, kw, kw, 1.0f, col, half, z1, z2);
       float ftt[C];
       gather_ft(z3, half, ftt);
 #pragma unroll
@@ -387,15 +388,18 @@ extern "C" size_t fiode_certify_workspace_bytes(int64_t G, int32_t batches) {
   return al(FIODE_M * 4) + al((size_t)G * C * 4) + al(nb * 4) + al(nb * 8);
 }
 
-extern "C" int fiode_certify(void* stream, const fiode_certify_config* cfg, const fiode_dyn_config* dyn,
-                             const fiode_dyn_weights* w, const float* x_feat, const uint8_t* grid, int64_t G,
-                             float* out, int32_t* exit_iters, void* workspace, size_t workspace_bytes) {
+extern "C" int fiode_certify_act(void* stream, const fiode_certify_config* cfg, const fiode_dyn_config* dyn,
+                                 const fiode_dyn_weights* w, const float* x_feat, const uint8_t* grid, int64_t G,
+                                 float* out, int32_t* exit_iters, void* workspace, size_t workspace_bytes,
+                                 int32_t activation) {
   if (!cfg || !dyn || !w || !x_feat || !grid || !out || !workspace) return FIODE_EINVAL;
+  if (activation != FIODE_ACT_RELU && activation != FIODE_ACT_GROUPSORT) return FIODE_EINVAL;
   if (dyn->n_hidden != C || dyn->mlp_size != M || dyn->x_dim != FIODE_X) return FIODE_ESHAPE;
   if (cfg->n_classes != C) return FIODE_ESHAPE;
   if (dyn->qp_max_iter < 1 || dyn->qp_max_iter > 32) return FIODE_EINVAL;
   if (cfg->label < 0 || cfg->label >= C || cfg->T <= 0 || cfg->batches <= 0 || !(cfg->min_std > 0.f)) return FIODE_EINVAL;
   if (G < cfg->batches || G >= (1LL << 32)) return FIODE_EINVAL;
+  if (cfg->T > MAXT) return FIODE_EINVAL;
   if (workspace_bytes < fiode_certify_workspace_bytes(G, cfg->batches)) return FIODE_EWORKSPACE;
   CertArgs a{};
   a.G = (uint32_t)G;
@@ -403,7 +407,6 @@ extern "C" int fiode_certify(void* stream, const fiode_certify_config* cfg, cons
   a.nb = cfg->batches + ((G % cfg->batches) != 0 ? 1 : 0);
   a.label = cfg->label;
   a.T = cfg->T;
-  if (cfg->T > MAXT) return FIODE_EINVAL;
   for (int v = 0; v <= cfg->T; ++v) a.etab[v] = (float)((double)v / (double)cfg->T);
   a.eps_g = (float)(1.0 / cfg->T);                                   // certify_lipschitz.py:78
   a.dist = (float)(sqrt((double)C) / cfg->T);                        // :81
@@ -435,7 +438,9 @@ extern "C" int fiode_certify(void* stream, const fiode_certify_config* cfg, cons
     ncu = 256;
   const uint32_t cap = 2u * (uint32_t)(ncu > 0 ? ncu : 256);
   if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(k_cert_fwd, dim3(blocks), dim3(256), ((size_t)(M + C) * LDQ + MAXT + 1) * sizeof(float), st, a);
+  const size_t flds = ((size_t)(M + C) * LDQ + MAXT + 1) * sizeof(float);
+  if (activation == FIODE_ACT_GROUPSORT) hipLaunchKernelGGL(k_cert_fwd<GROUPSORT>, dim3(blocks), dim3(256), flds, st, a);
+  else hipLaunchKernelGGL(k_cert_fwd<RELU>, dim3(blocks), dim3(256), flds, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
   uint32_t fblocks = (a.G + 255) / 256;
   if (fblocks > 8u * (uint32_t)ncu) fblocks = 8u * (uint32_t)ncu;      // persistent: 8 workgroups per CU
@@ -444,4 +449,11 @@ extern "C" int fiode_certify(void* stream, const fiode_certify_config* cfg, cons
   hipLaunchKernelGGL(k_cert_decode, dim3(1), dim3(64), 0, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
   return FIODE_OK;
+}
+
+extern "C" int fiode_certify(void* stream, const fiode_certify_config* cfg, const fiode_dyn_config* dyn,
+                             const fiode_dyn_weights* w, const float* x_feat, const uint8_t* grid, int64_t G,
+                             float* out, int32_t* exit_iters, void* workspace, size_t workspace_bytes) {
+  return fiode_certify_act(stream, cfg, dyn, w, x_feat, grid, G, out, exit_iters, workspace, workspace_bytes,
+                           FIODE_ACT_RELU);
 }

@@ -251,6 +251,8 @@ __device__ __forceinline__ void stage_input(const OsArgs& a, const StageIn& in, 
 
 // ---- one eval: k[kdst] = eval_dot(stage input) for every row of the batch -------------------
 // Uses exchange epochs ep (and ep + 1 after a resume); returns the next free epoch.
+// A: the MLP's activation (tile16.h; GROUPSORT regroups the layer-2 blocks of the waves).
+template <Act A>
 __device__ __noinline__ unsigned os_eval(const OsArgs& a, const float* Q2s, const float* Q3s, OsShared& sh, OsTile* tl,
                                     unsigned ep, int kdst, StageIn in) {
   const int lane = threadIdx.x & 63, q = lane >> 4, j = lane & 15;
@@ -260,7 +262,7 @@ __device__ __noinline__ unsigned os_eval(const OsArgs& a, const float* Q2s, cons
   const int kspec = min(last, sh.kprev + 3);
   const uint32_t ones[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
   T16W w;                     // this wave's weight operands, from the workgroup's LDS images
-  load_t16w(sh.Q1s, Q2s, LDQ, Q3s, LDQ, a.b2, a.b3, p, q, j, w);
+  load_t16w<A>(sh.Q1s, Q2s, LDQ, Q3s, LDQ, a.b2, a.b3, p, q, j, w);
   uint32_t wconv = 0xFFFFFFFFu;
   for (int t = 0; t < a.T; ++t) {
     const int tile = blockIdx.x * a.T + t;
@@ -275,7 +277,7 @@ __device__ __noinline__ unsigned os_eval(const OsArgs& a, const float* Q2s, cons
       const f32x4 uv = *reinterpret_cast<const f32x4*>(a.u + (size_t)bb * M + 16 * hb + 4 * q);
       uacc[hb] = f32x4v{uv[0], uv[1], uv[2], uv[3]};
     }
-    mlp16_part(w, uacc, h, ones, 0xFFFFFFFFu, 1.0f, p, q, nullptr, nullptr, &sh.zpart[p][lane][0]);
+    mlp16_part<false, A>(w, uacc, h, ones, 0xFFFFFFFFu, 1.0f, p, q, nullptr, nullptr, &sh.zpart[p][lane][0]);
     __syncthreads();
     float ft[C];
     ft16_sum(sh.zpart, j, ft);
@@ -369,6 +371,7 @@ __device__ __forceinline__ void for_own_rows(const OsArgs& a, Fn fn) {
   }
 }
 
+template <Act A>
 __device__ void os_rk4(const OsArgs& a, const float* Q2s, const float* Q3s, OsShared& sh, OsTile* tl) {
   // FixedGridODESolver grid in float32: niters = ceil((t1-t0)/h + 1), t_k = k*h + t0, last = t1
   unsigned ep = 1;
@@ -384,10 +387,10 @@ __device__ void os_rk4(const OsArgs& a, const float* Q2s, const float* Q3s, OsSh
     const float ta = (float)it * hs + t0;
     const float tb = (it + 2 == niters) ? t1 : (float)(it + 1) * hs + t0;
     const float dt = tb - ta;
-    ep = os_eval(a, Q2s, Q3s, sh, tl, ep, 0, StageIn{IN_Y, 0, dt});
-    ep = os_eval(a, Q2s, Q3s, sh, tl, ep, 1, StageIn{IN_RK4_2, 0, dt});
-    ep = os_eval(a, Q2s, Q3s, sh, tl, ep, 2, StageIn{IN_RK4_3, 0, dt});
-    ep = os_eval(a, Q2s, Q3s, sh, tl, ep, 3, StageIn{IN_RK4_4, 0, dt});
+    ep = os_eval<A>(a, Q2s, Q3s, sh, tl, ep, 0, StageIn{IN_Y, 0, dt});
+    ep = os_eval<A>(a, Q2s, Q3s, sh, tl, ep, 1, StageIn{IN_RK4_2, 0, dt});
+    ep = os_eval<A>(a, Q2s, Q3s, sh, tl, ep, 2, StageIn{IN_RK4_3, 0, dt});
+    ep = os_eval<A>(a, Q2s, Q3s, sh, tl, ep, 3, StageIn{IN_RK4_4, 0, dt});
     const int j0 = jo;
     while (jo < a.n_times && tb >= (float)a.times[jo]) ++jo;   // outputs in (ta, tb], uniform
     for_own_rows(a, [&](int b) {
@@ -419,13 +422,14 @@ __device__ void os_rk4(const OsArgs& a, const float* Q2s, const float* Q3s, OsSh
 
 __device__ __forceinline__ float rms_from_sum(double sumsq, size_t n) { return (float)sqrt(sumsq / (double)n); }
 
+template <Act A>
 __device__ void os_dopri5(const OsArgs& a, const float* Q2s, const float* Q3s, OsShared& sh, OsTile* tl) {
   unsigned ep = 1;
   const size_t BC = (size_t)a.B * C;
   const float rtol = (float)a.rtol, atol = (float)a.atol;
   const float* K0 = a.K;
   // ---- _select_initial_step(order - 1 = 4), float32 -------------------------------------------
-  ep = os_eval(a, Q2s, Q3s, sh, tl, ep, 0, StageIn{IN_Y, 0, 0.f});
+  ep = os_eval<A>(a, Q2s, Q3s, sh, tl, ep, 0, StageIn{IN_Y, 0, 0.f});
   double s01[2] = {0.0, 0.0};
   for_own_rows(a, [&](int b) {
     float y[C], f0[C];
@@ -443,7 +447,7 @@ __device__ void os_dopri5(const OsArgs& a, const float* Q2s, const float* Q3s, O
   const float d0 = rms_from_sum(s01[0], BC);
   const float d1 = rms_from_sum(s01[1], BC);
   const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : (0.01f * d0) / d1;
-  ep = os_eval(a, Q2s, Q3s, sh, tl, ep, 1, StageIn{IN_H0, 0, h0});      // f1 at t0 + h0
+  ep = os_eval<A>(a, Q2s, Q3s, sh, tl, ep, 1, StageIn{IN_H0, 0, h0});      // f1 at t0 + h0
   double s2[1] = {0.0};
   for_own_rows(a, [&](int b) {
     float y[C], f0[C], f1[C];
@@ -481,7 +485,7 @@ __device__ void os_dopri5(const OsArgs& a, const float* Q2s, const float* Q3s, O
       ++nsteps;
       const float dt32 = (float)dt;
       for (int i = 0; i < 6; ++i) {
-        ep = os_eval(a, Q2s, Q3s, sh, tl, ep, i + 1, StageIn{IN_DP, i, dt32});
+        ep = os_eval<A>(a, Q2s, Q3s, sh, tl, ep, i + 1, StageIn{IN_DP, i, dt32});
       }
       // y1 = the stage-6 input (FSAL tableau); batch-global RMS error ratio
       double ps[1] = {0.0};
@@ -593,6 +597,7 @@ __global__ __launch_bounds__(256) void k_os_clear(OsArgs a, int nslots) {
   if (i < 4) a.dstats[i] = 0.0;
 }
 
+template <Act A>
 __global__ __launch_bounds__(256) void k_ode_tiles(OsArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Q2s = smem;
@@ -621,8 +626,8 @@ __global__ __launch_bounds__(256) void k_ode_tiles(OsArgs a) {
     a.sol[o] = a.h0[o];
   }
   __syncthreads();
-  if (a.method == FIODE_ODE_RK4) os_rk4(a, Q2s, Q3s, sh, tl);
-  else os_dopri5(a, Q2s, Q3s, sh, tl);
+  if (a.method == FIODE_ODE_RK4) os_rk4<A>(a, Q2s, Q3s, sh, tl);
+  else os_dopri5<A>(a, Q2s, Q3s, sh, tl);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     a.stats[4] = sh.kprev;
     a.stats[6] = (int)gridDim.x;
@@ -654,7 +659,10 @@ size_t os_lds_bytes(int T) {
   return (size_t)(M + 32) * LDQ * sizeof(float) + sizeof(OsShared) + (size_t)T * sizeof(OsTile);
 }
 
-// resident workgroups of k_ode_tiles on this device (cached per device): CUs x occupancy
+// resident workgroups of k_ode_tiles<A> on this device (cached per device and instantiation: the
+// workgroups of the launched kernel wait on each other, so the grid is sized by ITS occupancy):
+// CUs x occupancy
+template <Act A>
 int os_capacity(size_t lds) {
   static int cached[64][2];
   int dev = 0;
@@ -662,7 +670,7 @@ int os_capacity(size_t lds) {
   if (dev < 64 && cached[dev][0] > 0 && (size_t)cached[dev][1] == lds) return cached[dev][0];
   int cus = 0, occ = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -1;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_ode_tiles, 256, lds) != hipSuccess) return -1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_ode_tiles<A>, 256, lds) != hipSuccess) return -1;
   const int cap = cus * (occ > 0 ? occ : 0);
   if (dev < 64) {
     cached[dev][0] = cap;
@@ -678,10 +686,13 @@ extern "C" size_t fiode_odeint_workspace_bytes(int32_t batch) {
   return os_layout(batch).total;
 }
 
-extern "C" int fiode_odeint(void* stream, const fiode_ode_config* cfg, const fiode_dyn_config* dyn,
-                            const fiode_dyn_weights* w, const float* x_feat, const float* h0, const double* times,
-                            float* solution, int32_t* stats, double* dstats, void* workspace, size_t workspace_bytes) {
+extern "C" int fiode_odeint_act(void* stream, const fiode_ode_config* cfg, const fiode_dyn_config* dyn,
+                                const fiode_dyn_weights* w, const float* x_feat, const float* h0,
+                                const double* times, float* solution, int32_t* stats, double* dstats,
+                                void* workspace, size_t workspace_bytes, int32_t activation) {
   if (!cfg || !dyn || !w) return FIODE_EINVAL;
+  if (activation != FIODE_ACT_RELU && activation != FIODE_ACT_GROUPSORT) return FIODE_EINVAL;
+  const bool gs = activation == FIODE_ACT_GROUPSORT;
   if (dyn->n_hidden != C || dyn->mlp_size != M || dyn->x_dim != FIODE_X) return FIODE_ESHAPE;
   if (dyn->qp_max_iter < 1 || dyn->qp_max_iter > 32) return FIODE_EINVAL;
   if (cfg->batch <= 0 || cfg->batch > FIODE_ODEINT_MAX_BATCH || cfg->n_times < 2) return FIODE_EINVAL;
@@ -703,7 +714,7 @@ extern "C" int fiode_odeint(void* stream, const fiode_ode_config* cfg, const fio
   a.drop_block = fiode_internal::debug_drop_publish();
   // tiles -> workgroups: one tile per workgroup while they fit the resident capacity, else T each
   a.ntiles = (a.B + TR - 1) / TR;
-  const int cap = os_capacity(os_lds_bytes(OS_TMAX));
+  const int cap = gs ? os_capacity<GROUPSORT>(os_lds_bytes(OS_TMAX)) : os_capacity<RELU>(os_lds_bytes(OS_TMAX));
   if (cap <= 0) return FIODE_EHIP;
   a.T = (a.ntiles + cap - 1) / cap;
   if (a.T > OS_TMAX) return FIODE_EINVAL;
@@ -720,7 +731,15 @@ extern "C" int fiode_odeint(void* stream, const fiode_ode_config* cfg, const fio
   const int nslots = (int)((L.total - L.xm) / 8);
   hipLaunchKernelGGL(k_os_clear, dim3((nslots + 255) / 256), dim3(256), 0, st, a, nslots);
   FIODE_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_ode_tiles, dim3(grid), dim3(256), os_lds_bytes(a.T), st, a);
+  if (gs) hipLaunchKernelGGL(k_ode_tiles<GROUPSORT>, dim3(grid), dim3(256), os_lds_bytes(a.T), st, a);
+  else hipLaunchKernelGGL(k_ode_tiles<RELU>, dim3(grid), dim3(256), os_lds_bytes(a.T), st, a);
   FIODE_HIP_CHECK(hipGetLastError());
   return FIODE_OK;
+}
+
+extern "C" int fiode_odeint(void* stream, const fiode_ode_config* cfg, const fiode_dyn_config* dyn,
+                            const fiode_dyn_weights* w, const float* x_feat, const float* h0, const double* times,
+                            float* solution, int32_t* stats, double* dstats, void* workspace, size_t workspace_bytes) {
+  return fiode_odeint_act(stream, cfg, dyn, w, x_feat, h0, times, solution, stats, dstats, workspace, workspace_bytes,
+                          FIODE_ACT_RELU);
 }

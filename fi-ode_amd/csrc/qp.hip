@@ -80,6 +80,7 @@ __global__ __launch_bounds__(128) void k_dyn_static(DynEvalArgs a) {
   a.u[(size_t)b * M + i] = (s + a.bx[i]) + a.b1[i];
 }
 
+template <Act A>
 __global__ __launch_bounds__(256) void k_dyn_fwd(DynEvalArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Q2s = smem;
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(256) void k_dyn_fwd(DynEvalArgs a) {
     float h[C];
     load_row10(a.h + (size_t)rr * C, h);
     f32x16 z1[4], z2[4];
-    const f32x16 z3 = mlp_tile<false>(Q2s, Q3s, q1, a.u + (size_t)b * M, a.b2, a.b3, h, kw, kw, 1.0f, col, half, z1, z2);
+    const f32x16 z3 = mlp_tile<false, A>(Q2s, Q3s, q1, a.u + (size_t)b * M, a.b2, a.b3, h, kw, kw, 1.0f, col, half, z1, z2);
     float ft[C], lower[C], nominal[C], sig[C], span[C], v[C], mu;
     gather_ft(z3, half, ft);
     barrier_nominal(a.d, h, ft, lower, nominal, sig, span);
@@ -169,10 +170,12 @@ extern "C" size_t fiode_dyn_eval_workspace_bytes(int32_t n) {
   return al(16) + al((size_t)n * M * 4) + al((size_t)n * C * 4);
 }
 
-extern "C" int fiode_dyn_eval(void* stream, const fiode_dyn_config* dyn, const fiode_dyn_weights* w, int32_t batch,
-                              int32_t rows_per_image, const float* x_feat, const float* h, float* f,
-                              int32_t* exit_iter, void* workspace, size_t workspace_bytes) {
+extern "C" int fiode_dyn_eval_act(void* stream, const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
+                                  int32_t batch, int32_t rows_per_image, const float* x_feat, const float* h,
+                                  float* f, int32_t* exit_iter, void* workspace, size_t workspace_bytes,
+                                  int32_t activation) {
   if (!dyn || !w) return FIODE_EINVAL;
+  if (activation != FIODE_ACT_RELU && activation != FIODE_ACT_GROUPSORT) return FIODE_EINVAL;
   if (dyn->n_hidden != C || dyn->mlp_size != M || dyn->x_dim != FIODE_X) return FIODE_ESHAPE;
   if (dyn->qp_max_iter < 1 || dyn->qp_max_iter > 32) return FIODE_EINVAL;
   if (batch < 0 || rows_per_image <= 0) return FIODE_EINVAL;
@@ -198,12 +201,21 @@ extern "C" int fiode_dyn_eval(void* stream, const fiode_dyn_config* dyn, const f
   hipLaunchKernelGGL(k_dyn_static, dim3(batch), dim3(128), 0, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
   const int ntiles = (n + 31) / 32;
-  hipLaunchKernelGGL(k_dyn_fwd, dim3((ntiles + FIODE_WAVES - 1) / FIODE_WAVES), dim3(256),
-                     (size_t)(M + 32) * LDQ * sizeof(float), st, a);
+  const dim3 fgrid((ntiles + FIODE_WAVES - 1) / FIODE_WAVES);
+  const size_t flds = (size_t)(M + 32) * LDQ * sizeof(float);
+  if (activation == FIODE_ACT_GROUPSORT) hipLaunchKernelGGL(k_dyn_fwd<GROUPSORT>, fgrid, dim3(256), flds, st, a);
+  else hipLaunchKernelGGL(k_dyn_fwd<RELU>, fgrid, dim3(256), flds, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_dyn_final, dim3((n + 255) / 256), dim3(256), 0, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
   return FIODE_OK;
+}
+
+extern "C" int fiode_dyn_eval(void* stream, const fiode_dyn_config* dyn, const fiode_dyn_weights* w, int32_t batch,
+                              int32_t rows_per_image, const float* x_feat, const float* h, float* f,
+                              int32_t* exit_iter, void* workspace, size_t workspace_bytes) {
+  return fiode_dyn_eval_act(stream, dyn, w, batch, rows_per_image, x_feat, h, f, exit_iter, workspace, workspace_bytes,
+                            FIODE_ACT_RELU);
 }
 
 extern "C" const char* fiode_error_string(int code) {

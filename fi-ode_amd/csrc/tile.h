@@ -38,6 +38,26 @@ __device__ __forceinline__ void dropout_relu(f32x16& z, uint32_t kw, int half, f
   }
 }
 
+// The activation of the MLP's two hidden layers, a compile-time parameter of the tile code.
+// GROUPSORT (group size 2 over the halves, cayley.py GroupSort): with a = z[:M/2], b = z[M/2:] the
+// output is cat(max(a, b), min(a, b)) -- unit u pairs with unit u + M/2.  Eval mode only (no
+// dropout); the training kernels instantiate RELU.
+enum Act { RELU = 0, GROUPSORT = 1 };
+
+// GroupSort on the four accumulator blocks of a 32-row wave tile, in place.  Block mb holds units
+// 32 mb .. 32 mb + 31 and register r of a lane is the same (unit offset, sample) in every block, so
+// the pair (u, u + 64) is z[mb][r] / z[mb + 2][r] of one lane: 2 x 16 max/min, no exchange.
+__device__ __forceinline__ void groupsort_tile(f32x16 (&z)[4]) {
+#pragma unroll
+  for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float a = z[mb][r], b = z[mb + 2][r];
+      z[mb][r] = fmaxf(a, b);
+      z[mb + 2][r] = fminf(a, b);
+    }
+}
+
 // store one [32 hidden x 32 samples] accumulator block as rows of a sample-major [N][M] array
 __device__ __forceinline__ void store_acc_rows(float* base_row, int mb, int half, const f32x16& z) {
 #pragma unroll
@@ -69,8 +89,8 @@ __device__ __forceinline__ void gather_ft(const f32x16& z3, int half, float (&ft
 }
 
 // Layers 1-2 of the MLP of one wave tile: z1/z2 become the post-dropout-ReLU activations a1^T,
-// a2^T.  q1: hoisted layer-1 A operands.
-template <bool DROP = true>
+// a2^T.  q1: hoisted layer-1 A operands.  A: the activation (GROUPSORT: eval mode only).
+template <bool DROP = true, Act A = RELU>
 __device__ __forceinline__ void mlp12_tile(const float* Q2s, const float (&q1)[4][5], const float* u_row,
                                            const float* b2, const float (&h)[C], const uint32_t (&kw1)[4],
                                            const uint32_t (&kw2)[4], float scale, int col, int half, f32x16 (&z1)[4],
@@ -84,8 +104,13 @@ __device__ __forceinline__ void mlp12_tile(const float* Q2s, const float (&q1)[4
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) z1[mb] = mfma32(q1[mb][s], bs, z1[mb]);
   }
+  static_assert(A == RELU || !DROP, "GroupSort dynamics run in eval mode only (no dropout)");
+  if constexpr (A == GROUPSORT) {
+    groupsort_tile(z1);
+  } else {
 #pragma unroll
-  for (int mb = 0; mb < 4; ++mb) dropout_relu<DROP>(z1[mb], kw1[mb], half, scale);
+    for (int mb = 0; mb < 4; ++mb) dropout_relu<DROP>(z1[mb], kw1[mb], half, scale);
+  }
   // layer 2: z2 = b2 + Q2 a1
 #pragma unroll
   for (int mb = 0; mb < 4; ++mb) load_acc_rows(b2, mb, half, z2[mb]);
@@ -101,17 +126,21 @@ __device__ __forceinline__ void mlp12_tile(const float* Q2s, const float (&q1)[4
       }
     __builtin_amdgcn_sched_barrier(0);   // bound the LDS-read hoisting window to one k-block
   }
+  if constexpr (A == GROUPSORT) {
+    groupsort_tile(z2);
+  } else {
 #pragma unroll
-  for (int mb = 0; mb < 4; ++mb) dropout_relu<DROP>(z2[mb], kw2[mb], half, scale);
+    for (int mb = 0; mb < 4; ++mb) dropout_relu<DROP>(z2[mb], kw2[mb], half, scale);
+  }
 }
 
 // The MLP of one wave tile: layers 1-3, returns the layer-3 accumulator (mlp12_tile + layer 3).
-template <bool DROP = true>
+template <bool DROP = true, Act A = RELU>
 __device__ __forceinline__ f32x16 mlp_tile(const float* Q2s, const float* Q3s, const float (&q1)[4][5],
                                            const float* u_row, const float* b2, const float* b3,
                                            const float (&h)[C], const uint32_t (&kw1)[4], const uint32_t (&kw2)[4],
                                            float scale, int col, int half, f32x16 (&z1)[4], f32x16 (&z2)[4]) {
-  mlp12_tile<DROP>(Q2s, q1, u_row, b2, h, kw1, kw2, scale, col, half, z1, z2);
+  mlp12_tile<DROP, A>(Q2s, q1, u_row, b2, h, kw1, kw2, scale, col, half, z1, z2);
   // layer 3: z3 = b3 + Q3 a2 (rows >= 10 of the 32-row tile are zero weights)
   f32x16 z3;
 #pragma unroll

@@ -273,6 +273,10 @@ __device__ __forceinline__ uint32_t qp_bisect_tree(const float (&lower)[C], cons
 // the per-eval critical path.  q1: layer-1 A operands Q1[16 hb + j][4 s + q] (0 past C); q2: the
 // layer-2 A operands Q2[16 (2p + o) + j][16 hb + 4q .. + 3]; q3: layer 3's Q3[j][16 (2p + o) + 4q ..]
 // (0 for j >= C); b2 of the part's output blocks; b3 on part 0.
+// Layer-2 output blocks of part p: RELU 2p, 2p + 1; GROUPSORT p, p + 4 -- the pair (u, u + 64) of
+// the sort is then blocks (p, p + 4) of ONE wave, register for register; q2, q3 and b2 follow
+// (load_t16w<GROUPSORT>).  Layer 3 is a sum over all hidden units, so which wave holds which
+// blocks only regroups the four partials ft16_sum adds.
 struct T16W {
   float q1[8][3];
   f32x4 q2[2][8];
@@ -282,6 +286,7 @@ struct T16W {
 };
 
 // Q1 [M][C]; Q2 / Q3 with row strides ld2 / ld3 (global: M; the padded LDS images: LDQ).
+template <Act A = RELU>
 __device__ __forceinline__ void load_t16w(const float* Q1, const float* Q2, int ld2, const float* Q3, int ld3,
                                           const float* b2, const float* b3, int p, int q, int j, T16W& w) {
 #pragma unroll
@@ -290,11 +295,20 @@ __device__ __forceinline__ void load_t16w(const float* Q1, const float* Q2, int 
     for (int s = 0; s < 3; ++s) w.q1[hb][s] = 4 * s + q < C ? Q1[(16 * hb + j) * C + 4 * s + q] : 0.f;
 #pragma unroll
   for (int o = 0; o < 2; ++o) {
+    if constexpr (A == GROUPSORT) {
+      const int ob = p + 4 * o;
 #pragma unroll
-    for (int hb = 0; hb < 8; ++hb)
-      w.q2[o][hb] = *reinterpret_cast<const f32x4*>(Q2 + (16 * (2 * p + o) + j) * ld2 + 16 * hb + 4 * q);
-    w.q3[o] = j < C ? *reinterpret_cast<const f32x4*>(Q3 + j * ld3 + 16 * (2 * p + o) + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-    w.b2[o] = *reinterpret_cast<const f32x4*>(b2 + 16 * (2 * p + o) + 4 * q);
+      for (int hb = 0; hb < 8; ++hb)
+        w.q2[o][hb] = *reinterpret_cast<const f32x4*>(Q2 + (16 * ob + j) * ld2 + 16 * hb + 4 * q);
+      w.q3[o] = j < C ? *reinterpret_cast<const f32x4*>(Q3 + j * ld3 + 16 * ob + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+      w.b2[o] = *reinterpret_cast<const f32x4*>(b2 + 16 * ob + 4 * q);
+    } else {
+#pragma unroll
+      for (int hb = 0; hb < 8; ++hb)
+        w.q2[o][hb] = *reinterpret_cast<const f32x4*>(Q2 + (16 * (2 * p + o) + j) * ld2 + 16 * hb + 4 * q);
+      w.q3[o] = j < C ? *reinterpret_cast<const f32x4*>(Q3 + j * ld3 + 16 * (2 * p + o) + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+      w.b2[o] = *reinterpret_cast<const f32x4*>(b2 + 16 * (2 * p + o) + 4 * q);
+    }
   }
 #pragma unroll
   for (int t = 0; t < 4; ++t) w.b3[t] = (p == 0 && 4 * q + t < C) ? b3[4 * q + t] : 0.f;
@@ -324,11 +338,15 @@ __device__ __forceinline__ void l1_pair(const T16W& w, const f32x4v (&uacc)[8], 
 // kShareL1 (z1x: LDS [8][64][4], all 4 waves call with the same choice): layer 1 split over the
 // waves -- wave p computes blocks 2p, 2p+1 (6 MFMA instead of 24), they meet in LDS behind one
 // workgroup barrier and every wave reads the 8 blocks back; bit-identical to the replicated layer 1.
-template <bool kShareL1 = false>
+// A = GROUPSORT (eval mode: masks and scale ignored, nothing saved, layer 1 replicated): layer 1's
+// pair (u, u + 64) is blocks (hb, hb + 4), which every wave holds; layer 2's is the wave's own two
+// output blocks (p, p + 4; w from load_t16w<GROUPSORT>): both sorts are lane-local, no barrier.
+template <bool kShareL1 = false, Act A = RELU>
 __device__ __forceinline__ void mlp16_part(const T16W& w, const f32x4v (&uacc)[8], const float (&h)[C],
                                            const uint32_t (&kw1)[4], uint32_t kw2p, float scale, int p, int q,
                                            float* a1row, float* a2row, float* zpart_lane,
                                            float (*z1x)[64][4] = nullptr) {
+  static_assert(A == RELU || !kShareL1, "GroupSort: eval mode, layer 1 replicated on every wave");
   f32x4v z1[8];
   if constexpr (kShareL1) {
     const int lane = threadIdx.x & 63;
@@ -353,9 +371,20 @@ __device__ __forceinline__ void mlp16_part(const T16W& w, const f32x4v (&uacc)[8
 #pragma unroll
       for (int hb = 0; hb < 8; ++hb) z1[hb] = mfma16(w.q1[hb][s], bs, z1[hb]);
     }
+    if constexpr (A == GROUPSORT) {
 #pragma unroll
-    for (int hb = 0; hb < 8; ++hb) dropout_relu16(z1[hb], kw1[hb >> 1], hb, q, scale);
-    if (a1row) {
+      for (int hb = 0; hb < 4; ++hb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float x = z1[hb][r], y = z1[hb + 4][r];
+          z1[hb][r] = fmaxf(x, y);
+          z1[hb + 4][r] = fminf(x, y);
+        }
+    } else {
+#pragma unroll
+      for (int hb = 0; hb < 8; ++hb) dropout_relu16(z1[hb], kw1[hb >> 1], hb, q, scale);
+    }
+    if (A == RELU && a1row) {
 #pragma unroll
       for (int hb = 0; hb < 8; ++hb)
         if ((hb >> 1) == p)
@@ -373,11 +402,20 @@ __device__ __forceinline__ void mlp16_part(const T16W& w, const f32x4v (&uacc)[8
       for (int t = 0; t < 4; ++t) z2[o] = mfma16(w.q2[o][hb][t], z1[hb][t], z2[o]);
     }
   }
+  if constexpr (A == GROUPSORT) {
 #pragma unroll
-  for (int o = 0; o < 2; ++o) {
-    dropout_relu16(z2[o], kw2p, 2 * p + o, q, scale);
-    if (a2row)
-      *reinterpret_cast<f32x4*>(a2row + 16 * (2 * p + o) + 4 * q) = f32x4{z2[o][0], z2[o][1], z2[o][2], z2[o][3]};
+    for (int r = 0; r < 4; ++r) {
+      const float x = z2[0][r], y = z2[1][r];
+      z2[0][r] = fmaxf(x, y);
+      z2[1][r] = fminf(x, y);
+    }
+  } else {
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      dropout_relu16(z2[o], kw2p, 2 * p + o, q, scale);
+      if (a2row)
+        *reinterpret_cast<f32x4*>(a2row + 16 * (2 * p + o) + 4 * q) = f32x4{z2[o][0], z2[o][1], z2[o][2], z2[o][3]};
+    }
   }
   f32x4v z3 = f32x4v{w.b3[0], w.b3[1], w.b3[2], w.b3[3]};
 #pragma unroll

@@ -14,6 +14,7 @@ LIB_PATH = pathlib.Path(os.environ.get("FIODE_LIB", _HERE / "libfiode.so"))
 
 FIODE_SAMPLER_GIVEN, FIODE_SAMPLER_COMPOSITE, FIODE_SAMPLER_DECISION_BOUNDARY, FIODE_SAMPLER_TRAJECTORY = 0, 1, 2, 3
 FIODE_DROPOUT_OFF, FIODE_DROPOUT_GIVEN, FIODE_DROPOUT_PHILOX = 0, 1, 2
+FIODE_ACT_RELU, FIODE_ACT_GROUPSORT = 0, 1     # fiode_*_act: activation of the dynamics MLP
 
 class FiodeLibraryError(RuntimeError):
     pass
@@ -142,14 +143,21 @@ def _load():
         "fiode_dyn_eval_workspace_bytes": (ct.c_size_t, [ct.c_int32]),
         "fiode_dyn_eval": (ct.c_int, [_vp, ct.POINTER(DynConfig), ct.POINTER(DynWeights), ct.c_int32, ct.c_int32,
                                       _vp, _vp, _vp, _vp, _vp, ct.c_size_t]),
+        "fiode_dyn_eval_act": (ct.c_int, [_vp, ct.POINTER(DynConfig), ct.POINTER(DynWeights), ct.c_int32, ct.c_int32,
+                                          _vp, _vp, _vp, _vp, _vp, ct.c_size_t, ct.c_int32]),
         "fiode_odeint_workspace_bytes": (ct.c_size_t, [ct.c_int32]),
         "fiode_odeint": (ct.c_int, [_vp, ct.POINTER(OdeConfig), ct.POINTER(DynConfig), ct.POINTER(DynWeights),
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, ct.c_size_t]),
+        "fiode_odeint_act": (ct.c_int, [_vp, ct.POINTER(OdeConfig), ct.POINTER(DynConfig), ct.POINTER(DynWeights),
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, ct.c_size_t, ct.c_int32]),
         "fiode_certify_grid_rows": (ct.c_int64, [ct.c_int32, ct.c_int32]),
         "fiode_certify_grid": (ct.c_int, [_vp, ct.c_int32, ct.c_int32, _vp]),
         "fiode_certify_workspace_bytes": (ct.c_size_t, [ct.c_int64, ct.c_int32]),
         "fiode_certify": (ct.c_int, [_vp, ct.POINTER(CertifyConfig), ct.POINTER(DynConfig), ct.POINTER(DynWeights),
                                      _vp, _vp, ct.c_int64, _vp, _vp, _vp, ct.c_size_t]),
+        "fiode_certify_act": (ct.c_int, [_vp, ct.POINTER(CertifyConfig), ct.POINTER(DynConfig),
+                                         ct.POINTER(DynWeights), _vp, _vp, ct.c_int64, _vp, _vp, _vp, ct.c_size_t,
+                                         ct.c_int32]),
         "fiode_odetrain_evals": (ct.c_int32, [ct.POINTER(OdeTrainConfig)]),
         "fiode_odetrain_saved_offsets": (ct.c_int, [ct.POINTER(OdeTrainConfig), _vp]),
         "fiode_odetrain_workspace_bytes": (ct.c_size_t, [ct.POINTER(OdeTrainConfig)]),

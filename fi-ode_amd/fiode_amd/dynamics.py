@@ -3,9 +3,11 @@
 Mirror of dynamics/classification.py:31-132: same constructor fields, same submodule names and
 state_dict keys (hidden_to_mlp / mlp_to_mlp / mlp_to_hidden / U_x with weight, bias, alpha;
 buffer static_state), same methods.  ``eval_dot`` / ``eval_dot_light`` / ``ode_forward`` run the
-fused HIP kernels (MLP + barrier + bisection QP with the reference's batch-global exit); the
-training-mode eval_dot with dropout and autograd is fused into the Lyapunov step
-(``fiode_amd.lyapunov``), which is the only place the reference differentiates it.
+fused HIP kernels (MLP + barrier + bisection QP with the reference's batch-global exit) for
+``activation`` 'ReLU' or 'GroupSort'; the training-mode eval_dot with dropout and autograd is
+fused into the Lyapunov step (``fiode_amd.lyapunov``), which is the only place the reference
+differentiates it, and implements 'ReLU' only: training a GroupSort module raises
+NotImplementedError.
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .cayley import CayleyLinear, cayley_scaled
+from .cayley import CayleyLinear, GroupSort, cayley_scaled
 from .streams import prefetch, take
 
 
@@ -38,10 +40,17 @@ class OrthoClassDynProjectSimplexLips(nn.Module):
         if (n_hidden, mlp_size, x_dim) != (ops.C, ops.M, ops.X):
             raise NotImplementedError(f"libfiode is built for n_hidden=10, mlp_size=128, x_dim=10 "
                                       f"(got {n_hidden}, {mlp_size}, {x_dim})")
-        if activation != "ReLU":
-            raise NotImplementedError("the fused dynamics kernels implement activation='ReLU' "
-                                      "(the README training/certify commands); GroupSort is not built")
-        self.activation = nn.ReLU()
+        if activation == "ReLU":
+            self.activation = nn.ReLU()
+        elif activation == "GroupSort":
+            # classification.py:44-48 (the reference's config default): no parameters or buffers, so
+            # the state_dict keys are the ReLU module's.  Evaluation, ODE solves and certification
+            # only: the training kernels refuse it (ops.require_relu)
+            self.activation = GroupSort()
+        else:
+            raise NotImplementedError(f"activation {activation!r}: the fused dynamics kernels implement 'ReLU' "
+                                      "and, for evaluation, ODE solves and certification, 'GroupSort'")
+        self.activation_name = activation
         self.dropout = nn.Dropout(dropout)
         self.mlp_size = mlp_size
         self.n_hidden = n_hidden
@@ -96,7 +105,7 @@ class OrthoClassDynProjectSimplexLips(nn.Module):
     def dyn_cfg(self) -> ops.DynCfg:
         return ops.DynCfg(alpha_1=self.alpha_1, alpha_2=self.alpha_2, sigma_1=self.sigma_1,
                           scale_nominal=bool(self.scale_nominal), dropout=float(self.dropout.p),
-                          qp_max_iter=self.qp_max_iter, qp_tol=self.qp_tol)
+                          qp_max_iter=self.qp_max_iter, qp_tol=self.qp_tol, activation=self.activation_name)
 
     # -- reference methods ----------------------------------------------------------------------
     def _h_dot_raw(self, h, x):

@@ -74,6 +74,7 @@ class GraphTrainStep:
         dev = x.device
         if dev.type != "cuda":
             raise ValueError("GraphTrainStep needs ROCm device tensors")
+        module.require_trainable_dynamics("GraphTrainStep")     # before the warm-up or a capture
         self.module, self.opt, self.reducer, self.world, self.act = module, optimizer, reducer, world, act
         self.check_every, self.n_replays = int(check_every), 0
         self.piped, self.early = [], False

@@ -563,6 +563,7 @@ class LyapunovLearning(nn.Module):
 
     def compute_loss(self, x, y, batch_size=None, act="relu", h=None, masks=None, debug=False):
         """pl_modules.py:390-502 with the per-sample graph fused (LyapunovLossFn)."""
+        self.require_trainable_dynamics("LyapunovLearning.compute_loss")
         step_stream = torch.cuda.current_stream(x.device) if x.is_cuda else None
         with self.streams.scope(step_stream):
             return self._compute_loss(x, y, h=h, masks=masks, debug=debug)
@@ -628,6 +629,12 @@ class LyapunovLearning(nn.Module):
                     3: "dt underflow"}.get(status, "a cross-workgroup exchange timed out")
             raise RuntimeError(f"train_ode solve failed (status {status}: {what}); the step's loss is NaN")
 
+    def require_trainable_dynamics(self, what: str) -> None:
+        """The training kernels (the fused Lyapunov step, the train_ode solves) apply ReLU: a module
+        whose dynamics use another activation (GroupSort: evaluation, ODE solves and certification
+        only) must not reach them -- NotImplementedError, before any tensor is touched."""
+        ops.require_relu(self.dyn_fun.dyn_cfg(), what)
+
     def ode_plan(self, batch: int, masks: Optional[torch.Tensor] = None) -> dict:
         """Solver plan of the train_ode solve (make_solver_params(train_ode_solver, train_ode_tol),
         pl_modules.py:24-35): 'rk4' with options.step_size = tol, or 'dopri5' with rtol = atol = tol
@@ -635,6 +642,7 @@ class LyapunovLearning(nn.Module):
         capacity of the device solve: ``train_ode_max_attempts`` or what 4 GiB of workspace holds;
         torchdiffeq has no cap -- more attempts report status 2 and a NaN loss, which the step guard
         keeps away from the parameters; see check_device_status)."""
+        self.require_trainable_dynamics("LyapunovLearning.ode_plan")
         if self.use_adjoint:
             raise NotImplementedError("odeint_adjoint (SURVEY.md section 8f row 3)")
         if self.train_ode_solver not in ("rk4", "dopri5"):

@@ -30,11 +30,35 @@ class DynCfg:
     dropout: float = 0.5
     qp_max_iter: int = 30
     qp_tol: float = 1e-4
+    activation: str = "ReLU"   # "ReLU" | "GroupSort": not a fiode_dyn_config field, passed to fiode_*_act
 
     def to_c(self) -> L.DynConfig:
         return L.DynConfig(C, M, X, float(self.alpha_1), float(self.alpha_2), float(self.sigma_1),
                            int(bool(self.scale_nominal)), float(self.dropout), int(self.qp_max_iter),
                            float(self.qp_tol))
+
+
+ACTIVATIONS = {"ReLU": L.FIODE_ACT_RELU, "GroupSort": L.FIODE_ACT_GROUPSORT}
+
+
+def _act(dyn: DynCfg) -> int:
+    """FIODE_ACT_* of a DynCfg (eval, ODE solve, certification)."""
+    try:
+        return ACTIVATIONS[dyn.activation]
+    except (KeyError, TypeError):
+        raise ValueError(f"activation {dyn.activation!r}: the dynamics kernels implement "
+                         f"{sorted(ACTIVATIONS)}") from None
+
+
+TRAIN_RELU_ONLY = ("{what}: GroupSort dynamics are supported for evaluation, ODE solves and certification; "
+                   "training (the fused Lyapunov step and the train_ode solves) is not, it implements "
+                   "activation='ReLU' only")
+
+
+def require_relu(dyn: DynCfg, what: str) -> None:
+    """The training kernels apply ReLU: refuse any other activation before anything is launched."""
+    if dyn.activation != "ReLU":
+        raise NotImplementedError(TRAIN_RELU_ONLY.format(what=what))
 
 
 def _stream(dev: torch.device) -> ct.c_void_p:
@@ -137,6 +161,7 @@ def lyap_step(x_feat: torch.Tensor, y: torch.Tensor, weights: Dict[str, torch.Te
     of them, the reference's draw shapes) instead of the in-kernel Philox draws.
     ``debug``: also returns the per-row outputs, the Exp(1) variates the sampler used
     (``exp_draws``) and the dropout keep words (``keep_words`` int32 [4, N, 4])."""
+    require_relu(dyn, "lyap_step")
     dev = x_feat.device
     B = x_feat.shape[0]
     S = int(sample_size)
@@ -252,6 +277,7 @@ def qp_backward(g, v, mu, lower, nominal):
 def dyn_eval(h: torch.Tensor, x_feat: torch.Tensor, weights: Dict[str, torch.Tensor], dyn: DynCfg,
              rows_per_image: int = 1):
     """eval_dot in eval mode: f[N][C] for h[N][C]; row r uses x_feat[r // rows_per_image]."""
+    act = _act(dyn)
     dev = h.device
     n = h.shape[0]
     B = x_feat.shape[0]
@@ -265,9 +291,9 @@ def dyn_eval(h: torch.Tensor, x_feat: torch.Tensor, weights: Dict[str, torch.Ten
     lib = L.lib()
     ws = _Workspace.get(dev, lib.fiode_dyn_eval_workspace_bytes(n), "dyn")
     dc = dyn.to_c()
-    rc = lib.fiode_dyn_eval(_stream(dev), ct.byref(dc), ct.byref(cw), B, int(rows_per_image), x_feat.data_ptr(),
-                            h.data_ptr(), f.data_ptr(), it.data_ptr(), ws.data_ptr(), ws.numel())
-    L.check(rc, "fiode_dyn_eval")
+    rc = lib.fiode_dyn_eval_act(_stream(dev), ct.byref(dc), ct.byref(cw), B, int(rows_per_image), x_feat.data_ptr(),
+                                h.data_ptr(), f.data_ptr(), it.data_ptr(), ws.data_ptr(), ws.numel(), act)
+    L.check(rc, "fiode_dyn_eval_act")
     return f, it
 
 
@@ -276,6 +302,7 @@ def odeint_dyn(x_feat: torch.Tensor, h0: torch.Tensor, times: torch.Tensor, weig
                step_size: Optional[float] = None, max_steps: int = 100000):
     """fiode_odeint: solve dh/dt = eval_dot(h, x_feat) (eval mode) from h0 over ``times``.
     Returns (solution [T,B,C], stats int32[8], dstats float64[4]) -- all on the device."""
+    act = _act(dyn)
     dev = h0.device
     B = h0.shape[0]
     if B > L.FIODE_ODEINT_MAX_BATCH:
@@ -300,10 +327,10 @@ def odeint_dyn(x_feat: torch.Tensor, h0: torch.Tensor, times: torch.Tensor, weig
     lib = L.lib()
     ws = _Workspace.get(dev, lib.fiode_odeint_workspace_bytes(B), "ode")
     dc = dyn.to_c()
-    rc = lib.fiode_odeint(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), x_feat.data_ptr(), h0.data_ptr(),
-                          times.data_ptr(), sol.data_ptr(), stats.data_ptr(), dstats.data_ptr(), ws.data_ptr(),
-                          ws.numel())
-    L.check(rc, "fiode_odeint")
+    rc = lib.fiode_odeint_act(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), x_feat.data_ptr(),
+                              h0.data_ptr(), times.data_ptr(), sol.data_ptr(), stats.data_ptr(), dstats.data_ptr(),
+                              ws.data_ptr(), ws.numel(), act)
+    L.check(rc, "fiode_odeint_act")
     del ws_w
     return sol, stats, dstats
 
@@ -351,6 +378,7 @@ def odetrain_forward(x_feat: torch.Tensor, h0: torch.Tensor, weights: Dict[str, 
                      offset_dev: Optional[torch.Tensor] = None):
     """fiode_odetrain_forward: y(t1) of the train-mode RK4 solve.  Returns (y [B,C], stats int32[8],
     workspace) -- the workspace carries the saved activations to ``odetrain_backward``."""
+    require_relu(dyn, "odetrain_forward")
     dev = h0.device
     B = int(cfg.batch)
     if B > L.FIODE_ODE_MAX_BATCH:
@@ -412,6 +440,7 @@ def odetrain_status_word(ws: torch.Tensor, cfg: L.OdeTrainConfig) -> torch.Tenso
 def odetrain_backward(g_y: torch.Tensor, x_feat: torch.Tensor, weights: Dict[str, torch.Tensor], dyn: DynCfg,
                       cfg: L.OdeTrainConfig, ws: torch.Tensor, debug: bool = False):
     """fiode_odetrain_backward: dL/d(weights, x_feat) from dL/dy(t1).  Returns (grads, dbg_gft)."""
+    require_relu(dyn, "odetrain_backward")
     dev = g_y.device
     B = int(cfg.batch)
     g_y = _need(g_y.float(), "g_y", (B, C), torch.float32, dev)
@@ -435,6 +464,7 @@ def odetrain_backward_x(g_y: torch.Tensor, x_feat: torch.Tensor, weights: Dict[s
                         gx_add_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fiode_odetrain_backward_x: the adjoint sweep and dL/dx_feat [B, X] (+ gx_add * gx_add_scale,
     a device scalar).  ``odetrain_backward_weights`` on the same workspace completes the gradients."""
+    require_relu(dyn, "odetrain_backward_x")
     dev = g_y.device
     B = int(cfg.batch)
     g_y = _need(g_y.float(), "g_y", (B, C), torch.float32, dev)
@@ -457,6 +487,7 @@ def odetrain_backward_x(g_y: torch.Tensor, x_feat: torch.Tensor, weights: Dict[s
 def odetrain_backward_weights(x_feat: torch.Tensor, weights: Dict[str, torch.Tensor], dyn: DynCfg,
                               cfg: L.OdeTrainConfig, ws: torch.Tensor) -> Dict[str, torch.Tensor]:
     """fiode_odetrain_backward_weights: the eight weight gradients (after odetrain_backward_x)."""
+    require_relu(dyn, "odetrain_backward_weights")
     dev = x_feat.device
     B = int(cfg.batch)
     x_feat = _need(x_feat, "x_feat", (B, X), torch.float32, dev)
@@ -487,6 +518,7 @@ def certify_image(x_feat: torch.Tensor, label: int, grid: torch.Tensor, weights:
                   dyn: DynCfg, T: int = 40, batches: int = 10, eps: float = 0.141, min_std: float = 0.225):
     """One image of certify_lipschitz.py:104-143: returns (out [nb][2] = per-batch max violation and
     max violation_larger_T, exit_iters [nb]) on the device."""
+    act = _act(dyn)
     dev = grid.device
     G = grid.shape[0]
     x_feat = _need(x_feat.reshape(-1), "x_feat", (X,), torch.float32, dev)
@@ -499,9 +531,9 @@ def certify_image(x_feat: torch.Tensor, label: int, grid: torch.Tensor, weights:
     ws = _Workspace.get(dev, lib.fiode_certify_workspace_bytes(G, batches), "cert")
     cfg = L.CertifyConfig(C, int(T), int(batches), int(label), float(eps), float(min_std))
     dc = dyn.to_c()
-    rc = lib.fiode_certify(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), x_feat.data_ptr(), grid.data_ptr(),
-                           G, out.data_ptr(), it.data_ptr(), ws.data_ptr(), ws.numel())
-    L.check(rc, "fiode_certify")
+    rc = lib.fiode_certify_act(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), x_feat.data_ptr(),
+                               grid.data_ptr(), G, out.data_ptr(), it.data_ptr(), ws.data_ptr(), ws.numel(), act)
+    L.check(rc, "fiode_certify_act")
     del ws_w
     return out, it
 

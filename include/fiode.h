@@ -163,6 +163,23 @@ FIODE_API int fiode_dyn_eval(void* stream, const fiode_dyn_config* dyn, const fi
                    int32_t batch, int32_t rows_per_image, const float* x_feat, const float* h,
                    float* f, int32_t* exit_iter, void* workspace, size_t workspace_bytes);
 
+/* Activation of the dynamics MLP's two hidden layers (classification.py:44-48, 98, 100) for the
+ * eval-mode entry points below.  GROUPSORT (the reference's config default): over the M hidden
+ * units, with a = z[:M/2] and b = z[M/2:], the output is cat(max(a, b), min(a, b)).
+ * fiode_dyn_eval_act / fiode_odeint_act / fiode_certify_act take their base entry point's
+ * arguments followed by the activation; the base entry points are their FIODE_ACT_RELU case, and
+ * the workspace sizes are the same.  Any other activation returns FIODE_EINVAL; every argument
+ * check (the activation included) runs before the workspace-size check, and nothing is launched
+ * on an error.  FIODE_ABI_VERSION does not move for them: they are new symbols only, and the
+ * structs, the existing prototypes and their behaviour are unchanged, so a caller built against
+ * ABI 5 before they existed still binds and runs as before.  The training entry points
+ * (fiode_lyap_step, fiode_odetrain_*) implement ReLU only. */
+enum { FIODE_ACT_RELU = 0, FIODE_ACT_GROUPSORT = 1 };
+FIODE_API int fiode_dyn_eval_act(void* stream, const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
+                                 int32_t batch, int32_t rows_per_image, const float* x_feat, const float* h,
+                                 float* f, int32_t* exit_iter, void* workspace, size_t workspace_bytes,
+                                 int32_t activation);
+
 /* ---- ODE solves (models.py:211-242 IVP.integrate -> torchdiffeq.odeint) ------------------- */
 enum { FIODE_ODE_RK4 = 0, FIODE_ODE_DOPRI5 = 1 };
 #define FIODE_ODE_MAX_BATCH 4096          /* the differentiable train_ode solve (fiode_odetrain_*) */
@@ -191,6 +208,11 @@ FIODE_API int fiode_odeint(void* stream, const fiode_ode_config* cfg, const fiod
                            const fiode_dyn_weights* w, const float* x_feat, const float* h0,
                            const double* times, float* solution, int32_t* stats, double* dstats,
                            void* workspace, size_t workspace_bytes);
+
+FIODE_API int fiode_odeint_act(void* stream, const fiode_ode_config* cfg, const fiode_dyn_config* dyn,
+                               const fiode_dyn_weights* w, const float* x_feat, const float* h0,
+                               const double* times, float* solution, int32_t* stats, double* dstats,
+                               void* workspace, size_t workspace_bytes, int32_t activation);
 
 /* ---- Differentiable solve for train_ode (pl_modules.py:490-500; models.py:235-241) -----------
  * y_hat = odeint(IVP.h_dot, (h0,), [t0, t1], method, ...) with the dynamics in TRAIN mode (fresh
@@ -293,6 +315,11 @@ FIODE_API size_t fiode_certify_workspace_bytes(int64_t G, int32_t batches);
 FIODE_API int fiode_certify(void* stream, const fiode_certify_config* cfg, const fiode_dyn_config* dyn,
                             const fiode_dyn_weights* w, const float* x_feat, const uint8_t* grid, int64_t G,
                             float* out, int32_t* exit_iters, void* workspace, size_t workspace_bytes);
+
+FIODE_API int fiode_certify_act(void* stream, const fiode_certify_config* cfg, const fiode_dyn_config* dyn,
+                                const fiode_dyn_weights* w, const float* x_feat, const uint8_t* grid, int64_t G,
+                                float* out, int32_t* exit_iters, void* workspace, size_t workspace_bytes,
+                                int32_t activation);
 
 /* ---- Batched inverse of the Cayley maps (classification.py:282-293 convert_cayley ->
  * cayley(): (I + A)^-1 with A = U - U^H + V^H V; replaces torch.inverse / torch.linalg.inv) ---- */
