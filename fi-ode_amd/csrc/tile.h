@@ -58,6 +58,48 @@ __device__ __forceinline__ void groupsort_tile(f32x16 (&z)[4]) {
     }
 }
 
+// groupsort_tile that also returns the order of every pair, for the backward: bit 16 mb + r of gt is
+// a > b and of eq is a == b for the pair z[mb][r] / z[mb + 2][r] (the sorted values are the same).
+__device__ __forceinline__ void groupsort_tile_codes(f32x16 (&z)[4], uint32_t& gt, uint32_t& eq) {
+  gt = 0;
+  eq = 0;
+#pragma unroll
+  for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float a = z[mb][r], b = z[mb + 2][r];
+      gt |= (a > b ? 1u : 0u) << (16 * mb + r);
+      eq |= (a == b ? 1u : 0u) << (16 * mb + r);
+      z[mb][r] = fmaxf(a, b);
+      z[mb + 2][r] = fminf(a, b);
+    }
+}
+
+// Backward of the activation on the four accumulator blocks of a wave tile, in place: g holds
+// d/d(activation output) and becomes d/d(pre-activation).  RELU: g [a > 0] with a the activation
+// output.  GROUPSORT: the max / min gradients go back to the pair's members by the codes of
+// groupsort_tile_codes; a tie splits them in half (torch.maximum / minimum, sconv.hip gs_grad).
+template <Act A>
+__device__ __forceinline__ void act_backward_tile(const f32x16 (&a)[4], f32x16 (&g)[4], uint32_t gt, uint32_t eq) {
+  if constexpr (A == GROUPSORT) {
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float gmx = g[mb][r], gmn = g[mb + 2][r];
+        const bool first_max = (gt >> (16 * mb + r)) & 1u, tie = (eq >> (16 * mb + r)) & 1u;
+        const float halfsum = gmx / 2.0f + gmn / 2.0f;
+        g[mb][r] = tie ? halfsum : (first_max ? gmx : gmn);
+        g[mb + 2][r] = tie ? halfsum : (first_max ? gmn : gmx);
+      }
+  } else {
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) g[mb][r] = a[mb][r] > 0.f ? g[mb][r] : 0.f;
+  }
+}
+
 // store one [32 hidden x 32 samples] accumulator block as rows of a sample-major [N][M] array
 __device__ __forceinline__ void store_acc_rows(float* base_row, int mb, int half, const f32x16& z) {
 #pragma unroll
@@ -153,6 +195,56 @@ __device__ __forceinline__ f32x16 mlp_tile(const float* Q2s, const float* Q3s, c
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       // rows >= C of the layer-3 A operand are zero (the image may hold only C rows)
+      const f32x4 q = col < C ? *reinterpret_cast<const f32x4*>(Q3s + col * LDQ + 32 * kb + 8 * g + 4 * half)
+                              : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int t = 0; t < 4; ++t) z3 = mfma32(q[t], z2[kb][4 * g + t], z3);
+    }
+  return z3;
+}
+
+// mlp_tile<false, GROUPSORT> that also returns the sort codes of both hidden layers (codes[0..1]:
+// gt / eq of layer 1, codes[2..3]: of layer 2; the eval_dot backward).  The same operations in the
+// same order as mlp_tile, so z1 / z2 and the returned accumulator are the same bits.
+__device__ __forceinline__ f32x16 mlp_tile_groupsort_codes(const float* Q2s, const float* Q3s,
+                                                           const float (&q1)[4][5], const float* u_row,
+                                                           const float* b2, const float* b3, const float (&h)[C],
+                                                           int col, int half, f32x16 (&z1)[4], f32x16 (&z2)[4],
+                                                           uint32_t (&codes)[4]) {
+#pragma unroll
+  for (int mb = 0; mb < 4; ++mb) load_acc_rows(u_row, mb, half, z1[mb]);
+#pragma unroll
+  for (int s = 0; s < 5; ++s) {
+    const float bs = half ? h[2 * s + 1] : h[2 * s];
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) z1[mb] = mfma32(q1[mb][s], bs, z1[mb]);
+  }
+  groupsort_tile_codes(z1, codes[0], codes[1]);
+#pragma unroll
+  for (int mb = 0; mb < 4; ++mb) load_acc_rows(b2, mb, half, z2[mb]);
+#pragma unroll
+  for (int kb = 0; kb < 4; ++kb) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int mb = 0; mb < 4; ++mb) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(Q2s + (32 * mb + col) * LDQ + 32 * kb + 8 * g + 4 * half);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) z2[mb] = mfma32(q[t], z1[kb][4 * g + t], z2[mb]);
+      }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  groupsort_tile_codes(z2, codes[2], codes[3]);
+  f32x16 z3;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int i = acc_row(r, half);
+    z3[r] = i < C ? b3[i] : 0.f;
+  }
+#pragma unroll
+  for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
       const f32x4 q = col < C ? *reinterpret_cast<const f32x4*>(Q3s + col * LDQ + 32 * kb + 8 * g + 4 * half)
                               : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll

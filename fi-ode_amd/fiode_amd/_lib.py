@@ -59,6 +59,11 @@ class LyapGrads(ct.Structure):
     _fields_ = [(n, ct.c_void_p) for n in ("Q1", "b1", "Qx", "bx", "Q2", "b2", "Q3", "b3", "x_feat")]
 
 
+class DynEvalDebug(ct.Structure):
+    """fiode_dyn_eval_debug: optional per-row outputs of fiode_dyn_eval_backward (NULL = not written)."""
+    _fields_ = [(n, ct.c_void_p) for n in ("f", "qp_lower", "qp_nominal", "mu", "g_ftilde")]
+
+
 FIODE_ODE_RK4, FIODE_ODE_DOPRI5 = 0, 1
 FIODE_DTYPE_F32, FIODE_DTYPE_C64 = 0, 1
 FIODE_INV_MAX_N = 128
@@ -145,6 +150,10 @@ def _load():
                                       _vp, _vp, _vp, _vp, _vp, ct.c_size_t]),
         "fiode_dyn_eval_act": (ct.c_int, [_vp, ct.POINTER(DynConfig), ct.POINTER(DynWeights), ct.c_int32, ct.c_int32,
                                           _vp, _vp, _vp, _vp, _vp, ct.c_size_t, ct.c_int32]),
+        "fiode_dyn_eval_backward_workspace_bytes": (ct.c_size_t, [ct.c_int32, ct.c_int32]),
+        "fiode_dyn_eval_backward": (ct.c_int, [_vp, ct.POINTER(DynConfig), ct.POINTER(DynWeights), ct.c_int32,
+                                               ct.c_int32, _vp, _vp, _vp, _vp, _vp, ct.POINTER(LyapGrads),
+                                               ct.POINTER(DynEvalDebug), _vp, ct.c_size_t, ct.c_int32]),
         "fiode_odeint_workspace_bytes": (ct.c_size_t, [ct.c_int32]),
         "fiode_odeint": (ct.c_int, [_vp, ct.POINTER(OdeConfig), ct.POINTER(DynConfig), ct.POINTER(DynWeights),
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, ct.c_size_t]),

@@ -4,10 +4,14 @@ Mirror of dynamics/classification.py:31-132: same constructor fields, same submo
 state_dict keys (hidden_to_mlp / mlp_to_mlp / mlp_to_hidden / U_x with weight, bias, alpha;
 buffer static_state), same methods.  ``eval_dot`` / ``eval_dot_light`` / ``ode_forward`` run the
 fused HIP kernels (MLP + barrier + bisection QP with the reference's batch-global exit) for
-``activation`` 'ReLU' or 'GroupSort'; the training-mode eval_dot with dropout and autograd is
-fused into the Lyapunov step (``fiode_amd.lyapunov``), which is the only place the reference
-differentiates it, and implements 'ReLU' only: training a GroupSort module raises
-NotImplementedError.
+``activation`` 'ReLU' or 'GroupSort'.  In eval mode (or with dropout 0) they are differentiable like
+the reference's: with grad enabled and ``h``, ``x`` or a parameter requiring grad, the call goes
+through ``_EvalDotFn``, whose backward is the fused HIP vector-Jacobian product
+(``ops.dyn_eval_backward``) for both activations, and the gradients reach the parameters through
+``effective_weights()``' own autograd (the Cayley maps).  One derivative only: a double backward
+raises.  The training-mode eval_dot with dropout is fused, with its backward, into the Lyapunov
+step and the train_ode solve (``fiode_amd.lyapunov``), which implement 'ReLU' only: training a
+GroupSort module raises NotImplementedError.
 """
 from __future__ import annotations
 
@@ -16,10 +20,40 @@ from typing import Dict
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import ops
 from .cayley import CayleyLinear, GroupSort, cayley_scaled
 from .streams import prefetch, take
+
+
+class _EvalDotFn(torch.autograd.Function):
+    """eval_dot in eval mode over (h, x, effective weights): forward ``ops.dyn_eval``, backward
+    ``ops.dyn_eval_backward``.  It saves its inputs and the forward's device exit iteration only (the
+    backward recomputes the rest), so nothing depends on a workspace surviving in between."""
+
+    @staticmethod
+    def forward(ctx, dyn, rows, h, x, *ws):
+        w = dict(zip(ops.WEIGHT_KEYS, ws))
+        f, it = ops.dyn_eval(h, x, w, dyn, rows_per_image=rows)
+        ctx.save_for_backward(h, x, it, *ws)
+        ctx.dyn, ctx.rows = dyn, rows
+        return f
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            raise RuntimeError("eval_dot is differentiable once: its backward is a fused kernel with no "
+                               "derivative of its own (double backward / create_graph=True is not supported)")
+        return _EvalDotFn._vjp(ctx, g)
+
+    @staticmethod
+    @once_differentiable
+    def _vjp(ctx, g):
+        h, x, it, *ws = ctx.saved_tensors
+        g_h, grads = ops.dyn_eval_backward(g.contiguous().float(), h, x, dict(zip(ops.WEIGHT_KEYS, ws)), ctx.dyn,
+                                           rows_per_image=ctx.rows, exit_iter=it)
+        return (None, None, g_h, grads["x_feat"]) + tuple(grads[k] for k in ops.WEIGHT_KEYS)
 
 
 class LipsLinear(nn.Linear):
@@ -119,8 +153,15 @@ class OrthoClassDynProjectSimplexLips(nn.Module):
     def _eval(self, h: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
         if self.training and self.dropout.p > 0:
             raise NotImplementedError("training-mode eval_dot (dropout) is fused into LyapunovLearning.compute_loss")
-        if torch.is_grad_enabled() and (h.requires_grad or x.requires_grad):
-            raise NotImplementedError("eval_dot is differentiated only inside the fused Lyapunov step")
+        if torch.is_grad_enabled() and (h.requires_grad or x.requires_grad or
+                                        any(p.requires_grad for p in self.parameters())):
+            n = h.shape[0]
+            rows = n // x.shape[0]
+            if rows * x.shape[0] != n:
+                raise ValueError("h rows must be a multiple of x rows")
+            w = self.effective_weights()
+            return _EvalDotFn.apply(self.dyn_cfg(), rows, h.contiguous().float(), x.contiguous().float(),
+                                    *[w[k].contiguous().float() for k in ops.WEIGHT_KEYS])
         with torch.no_grad():
             w = {k: v.detach().contiguous().float() for k, v in self.effective_weights().items()}
             n = h.shape[0]

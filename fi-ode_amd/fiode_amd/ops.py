@@ -297,6 +297,62 @@ def dyn_eval(h: torch.Tensor, x_feat: torch.Tensor, weights: Dict[str, torch.Ten
     return f, it
 
 
+def dyn_eval_backward(g_f: torch.Tensor, h: torch.Tensor, x_feat: torch.Tensor, weights: Dict[str, torch.Tensor],
+                      dyn: DynCfg, rows_per_image: int = 1, exit_iter=None, debug: bool = False):
+    """The vector-Jacobian product of ``dyn_eval`` (fiode_dyn_eval_backward): for ``g_f`` [N][C] =
+    dL/df returns (g_h [N][C], grads) with grads the eight effective-weight gradients and
+    ``x_feat`` [B][X].  ``exit_iter``: the int32 [1] device tensor ``dyn_eval`` returned for the same
+    inputs (read on the device), or an int.  Nothing else of the forward is needed: the kernel
+    recomputes it.  ``debug``: also returns the per-row f, qp_lower, qp_nominal, mu, g_ftilde."""
+    act = _act(dyn)
+    for name, t in (("g_f", g_f), ("h", h), ("x_feat", x_feat)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a tensor")
+    if h.dim() != 2 or h.shape[1] != C:
+        raise ValueError(f"h: shape {tuple(h.shape)}, expected (N, {C})")
+    if x_feat.dim() != 2 or x_feat.shape[1] != X:
+        raise ValueError(f"x_feat: shape {tuple(x_feat.shape)}, expected (B, {X})")
+    n, B = h.shape[0], x_feat.shape[0]
+    if int(rows_per_image) <= 0 or B * int(rows_per_image) != n:
+        raise ValueError("h rows must equal batch * rows_per_image")
+    if tuple(g_f.shape) != (n, C):
+        raise ValueError(f"g_f: shape {tuple(g_f.shape)}, expected {(n, C)}")
+    if exit_iter is None:
+        raise ValueError("exit_iter: pass the exit iteration dyn_eval returned (int32 [1] tensor) or an int")
+    dev = h.device
+    h = _need(h, "h", (n, C), torch.float32, dev)
+    g_f = _need(g_f, "g_f", (n, C), torch.float32, dev)
+    x_feat = _need(x_feat, "x_feat", (B, X), torch.float32, dev)
+    if isinstance(exit_iter, torch.Tensor):
+        exit_iter = _need(exit_iter.reshape(-1), "exit_iter", (1,), torch.int32, dev)
+    else:
+        exit_iter = torch.full((1,), int(exit_iter), dtype=torch.int32, device=dev)
+    ws_w, cw = _weights_c(weights, dev)
+    g_h = torch.empty_like(h)
+    grads = {k: torch.empty(WEIGHT_SHAPES[k], dtype=torch.float32, device=dev) for k in WEIGHT_KEYS}
+    grads["x_feat"] = torch.empty((B, X), dtype=torch.float32, device=dev)
+    dbg = {}
+    if debug:
+        dbg = {k: torch.empty((n, C), dtype=torch.float32, device=dev) for k in ("f", "qp_lower", "qp_nominal", "g_ftilde")}
+        dbg["mu"] = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        for v in grads.values():
+            v.zero_()
+        return (g_h, grads, dbg) if debug else (g_h, grads)
+    cd = L.DynEvalDebug(*[_ptr(dbg.get(k)) for k in ("f", "qp_lower", "qp_nominal", "mu", "g_ftilde")])
+    cg = L.LyapGrads(*[grads[k].data_ptr() for k in WEIGHT_KEYS + ("x_feat",)])
+    lib = L.lib()
+    ws = _Workspace.get(dev, lib.fiode_dyn_eval_backward_workspace_bytes(B, int(rows_per_image)), "dynbwd")
+    dc = dyn.to_c()
+    rc = lib.fiode_dyn_eval_backward(_stream(dev), ct.byref(dc), ct.byref(cw), B, int(rows_per_image),
+                                     x_feat.data_ptr(), h.data_ptr(), g_f.data_ptr(), exit_iter.data_ptr(),
+                                     g_h.data_ptr(), ct.byref(cg), ct.byref(cd) if debug else None,
+                                     ws.data_ptr(), ws.numel(), act)
+    L.check(rc, "fiode_dyn_eval_backward")
+    del ws_w
+    return (g_h, grads, dbg) if debug else (g_h, grads)
+
+
 def odeint_dyn(x_feat: torch.Tensor, h0: torch.Tensor, times: torch.Tensor, weights: Dict[str, torch.Tensor],
                dyn: DynCfg, method: str = "dopri5", rtol: float = 1e-3, atol: float = 1e-3,
                step_size: Optional[float] = None, max_steps: int = 100000):

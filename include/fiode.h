@@ -180,6 +180,32 @@ FIODE_API int fiode_dyn_eval_act(void* stream, const fiode_dyn_config* dyn, cons
                                  float* f, int32_t* exit_iter, void* workspace, size_t workspace_bytes,
                                  int32_t activation);
 
+/* The vector-Jacobian product of fiode_dyn_eval_act (the reference's eval_dot is an ordinary
+ * differentiable torch function, classification.py:104-126): given g_f [N][C] = d L / d f it writes
+ * g_h [N][C] = d L / d h and, into `grads` (all members required, overwritten), d L / d (effective
+ * weights) and d L / d x_feat [B][X].  Both activations.  Nothing is saved by the forward: the MLP is
+ * recomputed with the forward's own tile code (the same bits) and the QP is run to exit_iter[0], the
+ * device int32 that fiode_dyn_eval_act wrote for the same inputs (read on the device, no host sync;
+ * clamped to 0 .. qp_max_iter - 1).  The QP's Jacobian is the reference's closed form
+ * (barrier_projection.py:271-311); a GroupSort tie splits the gradient in half (torch.maximum /
+ * minimum).  dbg (nullable): optional per-row outputs, NULL members are not written.  Argument
+ * checks, error codes and batch == 0 as fiode_dyn_eval_act.  With this, the eval-mode dynamics are
+ * differentiable outside the training entry points (fiode_lyap_step, fiode_odetrain_*), which keep
+ * their own fused backward with dropout and implement ReLU only. */
+typedef struct fiode_dyn_eval_debug {
+  float* f;              /* [N][C] the recomputed eval_dot (bit-equal to the forward's)           */
+  float* qp_lower;       /* [N][C] QP lower bound                                                 */
+  float* qp_nominal;     /* [N][C] QP nominal                                                     */
+  float* mu;             /* [N] QP multiplier at exit_iter                                        */
+  float* g_ftilde;       /* [N][C] d L / d mlp_to_hidden output                                   */
+} fiode_dyn_eval_debug;
+FIODE_API size_t fiode_dyn_eval_backward_workspace_bytes(int32_t batch, int32_t rows_per_image);
+FIODE_API int fiode_dyn_eval_backward(void* stream, const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
+                                      int32_t batch, int32_t rows_per_image, const float* x_feat, const float* h,
+                                      const float* g_f, const int32_t* exit_iter, float* g_h,
+                                      fiode_lyap_grads* grads, const fiode_dyn_eval_debug* dbg, void* workspace,
+                                      size_t workspace_bytes, int32_t activation);
+
 /* ---- ODE solves (models.py:211-242 IVP.integrate -> torchdiffeq.odeint) ------------------- */
 enum { FIODE_ODE_RK4 = 0, FIODE_ODE_DOPRI5 = 1 };
 #define FIODE_ODE_MAX_BATCH 4096          /* the differentiable train_ode solve (fiode_odetrain_*) */
