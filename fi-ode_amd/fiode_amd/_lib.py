@@ -159,6 +159,11 @@ def _load():
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, ct.c_size_t]),
         "fiode_odeint_act": (ct.c_int, [_vp, ct.POINTER(OdeConfig), ct.POINTER(DynConfig), ct.POINTER(DynWeights),
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, ct.c_size_t, ct.c_int32]),
+        "fiode_odeint_backward_x_steps": (ct.c_int32, [ct.c_double, ct.c_double, ct.c_double]),
+        "fiode_odeint_backward_x_workspace_bytes": (ct.c_size_t, [ct.c_int32, ct.c_double, ct.c_double, ct.c_double]),
+        "fiode_odeint_backward_x": (ct.c_int, [_vp, ct.POINTER(DynConfig), ct.POINTER(DynWeights), ct.c_int32,
+                                               ct.c_double, ct.c_double, ct.c_double, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, ct.c_size_t, ct.c_int32]),
         "fiode_certify_grid_rows": (ct.c_int64, [ct.c_int32, ct.c_int32]),
         "fiode_certify_grid": (ct.c_int, [_vp, ct.c_int32, ct.c_int32, _vp]),
         "fiode_certify_workspace_bytes": (ct.c_size_t, [ct.c_int64, ct.c_int32]),

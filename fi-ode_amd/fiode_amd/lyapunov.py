@@ -13,6 +13,7 @@ validation_step, configure_optimizers, log, current_epoch, global_step).
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Optional
 
 import numpy as np
@@ -28,6 +29,27 @@ from .odeint import make_solver_params
 from .optim import FiodeAdam, FiodeAdamW
 from .sampling import CompositeSampler, CompositeSamplerScheduler, TrajectorySampler
 from .streams import StepStreams, current, prefetch, run_on, take
+
+
+@contextlib.contextmanager
+def no_param_grad(module: nn.Module):
+    """Inside: ``module`` in eval mode and none of its parameters requiring grad (advertorch's
+    ``ctx_noparamgrad_and_eval``).  With an input that requires grad, the native ODE solve then
+    takes its input-gradient route (``fiode_amd.odeint``) -- what an attack on the image needs.
+    Every ``requires_grad`` flag and every submodule's training mode are put back on exit, after
+    an exception too."""
+    flags = [(p, p.requires_grad) for p in module.parameters()]
+    modes = [(m, m.training) for m in module.modules()]
+    try:
+        for p, _ in flags:
+            p.requires_grad_(False)
+        module.eval()
+        yield module
+    finally:
+        for p, f in flags:
+            p.requires_grad_(f)
+        for m, t in modes:
+            m.training = t
 
 
 class LyapunovLossFn(torch.autograd.Function):
@@ -350,6 +372,8 @@ class LyapunovLearning(nn.Module):
         self.decay_epochs, self.betas = list(decay_epochs), (beta1, beta2)
         self.scheduler_name, self.max_epochs, self.warmup = scheduler_name, max_epochs, warmup
         self.simplex, self.act, self.eps, self.norm = simplex, act, eps, norm
+        self.val_adv = bool(val_adv)    # validation_step runs the reference's 5-step PGD (pl_modules.py:189-202)
+        self.val_adv_generator: Optional[torch.Generator] = None   # fixes the attack's random start (tests)
         self.epoch_off_scale = epoch_off_scale
         self.current_epoch = 0
         self.global_step = 0
@@ -393,11 +417,25 @@ class LyapunovLearning(nn.Module):
                           int_params=self.val_solver_params, use_adjoint=self.use_adjoint, return_traj=return_traj)
 
     def validation_step(self, batch, batch_idx=0):
-        """GeneralLearning.validation_step without attacks (val_adv=False, pl_modules.py:203-219)."""
+        """GeneralLearning.validation_step (pl_modules.py:185-220).  With ``val_adv`` the reference's
+        5-step PGD (L2 or Linf by ``norm``; eps, alpha = eps 2.5 / 10) attacks the batch first:
+        ``fiode_amd.attacks`` under ``no_param_grad(self)``, so the solves inside the attack take the
+        input-gradient route of ``fiode_amd.odeint``; the clean and the adversarial forward then run
+        without grad as before."""
         x, y = batch
-        with torch.no_grad():
-            net_out = self(x)
+        error_adv = None
+        if getattr(self, "val_adv", False):
+            adv_images = self.validation_attack(x, y)
+            with torch.no_grad():
+                net_out = self(x)
+                net_out_adv = self(adv_images)
+            error_adv = (net_out_adv.argmax(dim=-1) != y).float().mean()
+        else:
+            with torch.no_grad():
+                net_out = self(x)
         error = (net_out.argmax(dim=-1) != y).float().mean()
+        if error_adv is None:
+            error_adv = error
         if self.simplex:
             loss = F.nll_loss(torch.log(torch.clamp(net_out, min=1e-12)), y)
         else:
@@ -408,16 +446,32 @@ class LyapunovLearning(nn.Module):
         import torch.distributed as dist
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         if world > 1:
-            red = MetricReducer(["validation_loss", "validation_error"], loss.device).reduce(
-                {"validation_loss": loss, "validation_error": error}, world)
+            red = MetricReducer(["validation_loss", "validation_error", "validation_adv_error"], loss.device).reduce(
+                {"validation_loss": loss, "validation_error": error, "validation_adv_error": error_adv}, world)
             self.log("validation_loss", red["validation_loss"])
             self.log("validation_error", red["validation_error"])
-            self.log("validation_adv_error", red["validation_error"])
+            self.log("validation_adv_error", red["validation_adv_error"])
         else:
             self.log("validation_loss", loss)
             self.log("validation_error", error)
-            self.log("validation_adv_error", error)
+            self.log("validation_adv_error", error_adv)
         return loss
+
+    def validation_attack(self, x, y):
+        """The adversarial images of validation_step (pl_modules.py:189-195): PGDL2 for norm 'L2', PGD for
+        'Linf', eps = self.eps, alpha = eps 2.5 / 10, 5 steps, random start (``val_adv_generator``, if
+        set, fixes it).  Runs with grad enabled inside ``no_param_grad(self)``."""
+        from . import attacks
+        if self.norm == "L2":
+            cls = attacks.PGDL2
+        elif self.norm == "Linf":
+            cls = attacks.PGD
+        else:
+            raise ValueError(f"val_adv: norm {self.norm!r} (the reference attacks 'L2' and 'Linf')")
+        with no_param_grad(self), torch.enable_grad():
+            atk = cls(self, eps=self.eps, alpha=self.eps * 2.5 / 10, steps=5,
+                      generator=getattr(self, "val_adv_generator", None))
+            return atk(x, y)
 
     # Lightning-like surface -------------------------------------------------------------------
     @classmethod

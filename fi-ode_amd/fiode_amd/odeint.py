@@ -7,6 +7,12 @@ OrthoClassDynProjectSimplexLips, the whole solve runs as ONE persistent gfx950 k
 right-hand side (e.g. the 3-state Segway plumbing check of BASELINE config 1) runs the same two
 algorithms as plain torch ops on whatever device its tensors live on.
 
+The native solve runs without grad.  With grad enabled, ``h0`` or the static features requiring grad
+and no parameter of the dynamics requiring grad (``fiode_amd.lyapunov.no_param_grad``: an attack on
+the image), it is differentiable in its inputs: rk4 through ``fiode_odeint_backward_x``, dopri5 with
+ReLU through the train_ode dopri5 solve with dropout off, anything else through the torch steppers
+over the differentiable ``eval_dot`` (``_odeint_native_input_grad``).
+
 make_solver_params (pl_modules.py:24-35) is reproduced: adaptive solvers take rtol=atol=tol;
 fixed-grid solvers take options.step_size = tol.
 """
@@ -60,6 +66,16 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, **unuse
     return (sol,) if is_tuple else sol
 
 
+def _check_solve_status(stats, dstats):
+    status = int(stats[3])        # one host read per solve (torchdiffeq raises here too)
+    if status == 2:
+        raise RuntimeError(f"max_num_steps exceeded ({int(stats[5])} steps)")
+    if status == 3:
+        raise AssertionError(f"underflow in dt {float(dstats[0])}")
+    if status:
+        raise RuntimeError(f"fiode_odeint: cross-workgroup exchange timed out (status {status}); results invalid")
+
+
 def _odeint_native(dyn, h0, t, rtol, atol, method, options):
     from . import ops
     if dyn.static_state is None:
@@ -67,6 +83,9 @@ def _odeint_native(dyn, h0, t, rtol, atol, method, options):
     if dyn.training and dyn.dropout.p > 0:
         raise NotImplementedError("odeint through the training-mode (dropout) dynamics is not fused; "
                                   "validation/inference solves run in eval mode")
+    if (torch.is_grad_enabled() and (h0.requires_grad or dyn.static_state.requires_grad)
+            and not any(p.requires_grad for p in dyn.parameters())):
+        return _odeint_native_input_grad(dyn, h0, t, rtol, atol, method, options)
     times = t.detach().to(device=h0.device, dtype=torch.float64)
     with torch.no_grad():
         w = {k: v.detach().float().contiguous() for k, v in dyn.effective_weights().items()}
@@ -76,14 +95,127 @@ def _odeint_native(dyn, h0, t, rtol, atol, method, options):
                                             step_size=options.get("step_size"),
                                             max_steps=int(options.get("max_num_steps", 100000)))
     dyn.last_solve_stats = (stats, dstats)
-    status = int(stats[3])        # one host read per solve (torchdiffeq raises here too)
-    if status == 2:
-        raise RuntimeError(f"max_num_steps exceeded ({int(stats[5])} steps)")
-    if status == 3:
-        raise AssertionError(f"underflow in dt {float(dstats[0])}")
-    if status:
-        raise RuntimeError(f"fiode_odeint: cross-workgroup exchange timed out (status {status}); results invalid")
+    _check_solve_status(stats, dstats)
     return sol
+
+
+# ---- input gradients of the native solve (attacks on the image) ----------------------------------
+# Taken only with grad enabled, h0 or static_state requiring grad and NO dynamics parameter requiring
+# grad (fiode_amd.lyapunov.no_param_grad); everything else keeps the no-grad native solve above.
+
+_ONCE = ("the native ODE solve is differentiable once: its backward is a fused kernel with no derivative of its "
+         "own (double backward / create_graph=True is not supported)")
+
+
+class _OdeintRk4XFn(torch.autograd.Function):
+    """y(t1) of the eval-mode rk4 solve over (h0, static_state).  Forward: the native solve
+    (fiode_odeint_act) asked for its own grid as output times, so it also returns the step states
+    the backward needs and y(t1) is the no-grad solve's.  Backward: ``ops.odeint_backward_x``."""
+
+    @staticmethod
+    def forward(ctx, dyn_mod, plan, h0, x, *ws):
+        from . import ops
+        w = dict(zip(ops.WEIGHT_KEYS, ws))
+        grid = torch.from_numpy(ops.rk4_grid(plan["t0"], plan["t1"], plan["step_size"])).to(h0.device)
+        states, stats, dstats = ops.odeint_dyn(x, h0, grid, w, plan["dyn"], method="rk4",
+                                               step_size=plan["step_size"])
+        dyn_mod.last_solve_stats = (stats, dstats)
+        _check_solve_status(stats, dstats)
+        ctx.save_for_backward(states, x, *ws)
+        ctx.plan = plan
+        return states[-1].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            raise RuntimeError(_ONCE)
+        return _OdeintRk4XFn._vjp(ctx, g)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _vjp(ctx, g):
+        from . import ops
+        states, x, *ws = ctx.saved_tensors
+        p = ctx.plan
+        g_h0, g_x = ops.odeint_backward_x(g.contiguous().float(), x, states[0], dict(zip(ops.WEIGHT_KEYS, ws)),
+                                          p["dyn"], t0=p["t0"], t1=p["t1"], step_size=p["step_size"], states=states)
+        return (None, None, g_h0, g_x) + (None,) * len(ws)
+
+
+class _OdeintDopri5XFn(torch.autograd.Function):
+    """y(t1) of the dopri5 solve over static_state for ReLU dynamics: the differentiable train_ode
+    solve with dropout off (fiode_odetrain_forward / _backward_x), the exact gradient through the
+    step controller's accepted steps."""
+
+    @staticmethod
+    def forward(ctx, dyn_mod, plan, h0, x, *ws):
+        from . import ops
+        w = dict(zip(ops.WEIGHT_KEYS, ws))
+        y, stats, wsp = ops.odetrain_forward(x, h0, w, plan["dyn"], plan["cfg"])
+        status = max(int(stats[3]), int(ops.odetrain_status_word(wsp, plan["cfg"])[0]))
+        if status == 2:
+            raise RuntimeError("dopri5: the attempt capacity of the differentiable solve was exhausted")
+        if status == 3:
+            raise AssertionError("underflow in dt")
+        if status:
+            raise RuntimeError(f"fiode_odetrain: cross-workgroup exchange timed out (status {status}); results invalid")
+        ctx.save_for_backward(x, *ws)
+        ctx.plan, ctx.wsp = plan, wsp
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            raise RuntimeError(_ONCE)
+        return _OdeintDopri5XFn._vjp(ctx, g)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _vjp(ctx, g):
+        from . import ops
+        x, *ws = ctx.saved_tensors
+        g_x = ops.odetrain_backward_x(g.contiguous().float(), x, dict(zip(ops.WEIGHT_KEYS, ws)), ctx.plan["dyn"],
+                                      ctx.plan["cfg"], ctx.wsp)
+        ctx.wsp = None
+        return (None, None, None, g_x) + (None,) * len(ws)
+
+
+def _odeint_native_input_grad(dyn, h0, t, rtol, atol, method, options):
+    """The routes of a solve whose inputs, and only they, require grad:
+      rk4, outputs [t0, t1]:          native solve + fiode_odeint_backward_x (both activations);
+      dopri5, ReLU, outputs [t0, t1]: the train_ode dopri5 solve with dropout off + its backward_x
+                                      (d/d static_state; an h0 that requires grad goes the torch way);
+      anything else (dopri5 with GroupSort, more output times): the torch steppers over the
+      differentiable eval_dot -- correct and slow (one forward and one backward launch chain per
+      evaluation)."""
+    from . import ops
+    from . import _lib as L
+    x = dyn.static_state
+    cfg = dyn.dyn_cfg()
+    B = h0.shape[0]
+    end_points = t.numel() == 2
+    fn = plan = None
+    if method == "rk4" and end_points and options.get("step_size") is not None:
+        plan = dict(dyn=cfg, t0=float(t[0]), t1=float(t[-1]), step_size=float(options["step_size"]))
+        try:
+            ops.rk4_grid(plan["t0"], plan["t1"], plan["step_size"])
+            fn = _OdeintRk4XFn
+        except ValueError:
+            fn = None
+    elif (method == "dopri5" and end_points and cfg.activation == "ReLU" and not h0.requires_grad
+          and B <= L.FIODE_ODE_MAX_BATCH):
+        ocfg = ops.odetrain_config(B, float(t[0]), float(t[-1]), 0.0, L.FIODE_DROPOUT_OFF, method="dopri5",
+                                   rtol=float(rtol), atol=float(atol),
+                                   max_attempts=int(options.get("max_attempts", ops.odetrain_default_attempts(B))))
+        plan = dict(dyn=cfg, cfg=ocfg)
+        fn = _OdeintDopri5XFn
+    if fn is None:
+        return _odeint_torch(lambda tt, yy: dyn._eval(yy, x), h0.float(), t, rtol, atol, method, options)
+    with torch.no_grad():
+        ew = dyn.effective_weights()
+        w = [ew[k].detach().float().contiguous() for k in ops.WEIGHT_KEYS]
+    y = fn.apply(dyn, plan, h0.float().contiguous(), x.float().contiguous(), *w)
+    return torch.stack([h0.float(), y])
 
 
 # ---- generic torch steppers (same algorithms, any func / device) --------------------------------
@@ -157,7 +289,7 @@ def _dopri5_torch(F, y0, t, rtol, atol, options):
     d2 = _rms((f1 - f0) / scale) / h0
     h1 = torch.max(torch.tensor(1e-6, dtype=y.dtype), h0 * 1e-3) if (d1 <= 1e-15 and d2 <= 1e-15) \
         else (0.01 / max(d1, d2)) ** (1.0 / 5.0)
-    dt = float(torch.min(100 * h0, h1))
+    dt = float(torch.min(100 * h0, h1).detach())
     tcur, tprev, tnext = float(t[0]), float(t[0]), float(t[0])
     fcur, interp = f0, None
     sol = [y0]

@@ -391,6 +391,67 @@ def odeint_dyn(x_feat: torch.Tensor, h0: torch.Tensor, times: torch.Tensor, weig
     return sol, stats, dstats
 
 
+def rk4_grid(t0: float, t1: float, step_size: float) -> "np.ndarray":
+    """The float32 grid of the fixed-grid solve (torchdiffeq's _grid_constructor_from_step_size as
+    fiode_odeint forms it on the device: t_k = k h + t0 rounded per operation, the last point t1), as
+    float64 values.  Asked for as output times, the solve returns its step states."""
+    import numpy as np
+    n = L.lib().fiode_odeint_backward_x_steps(float(t0), float(t1), float(step_size))
+    if n < 1:
+        raise ValueError("rk4 grid: needs t1 > t0, step_size > 0 and at most 1024 steps")
+    g = np.arange(n + 1, dtype=np.float32) * np.float32(step_size) + np.float32(t0)
+    g[-1] = np.float32(t1)
+    if not np.all(np.diff(g) > 0):
+        raise ValueError("rk4 grid: step_size does not resolve in float32 over [t0, t1]")
+    return g.astype(np.float64)
+
+
+def odeint_backward_x(g_y: torch.Tensor, x_feat: torch.Tensor, h0: torch.Tensor, weights: Dict[str, torch.Tensor],
+                      dyn: DynCfg, *, t0: float, t1: float, step_size: float,
+                      states: Optional[torch.Tensor] = None, debug: bool = False):
+    """fiode_odeint_backward_x: for the eval-mode rk4 solve y(t1) = odeint(h_dot, h0, [t0, t1]) and
+    ``g_y`` [B,C] = dL/dy(t1), returns (g_h0 [B,C], g_x_feat [B,X]).  No weight gradients.
+    ``states`` [n_steps+1,B,C]: the step states of that solve (``odeint_dyn`` over ``rk4_grid`` as
+    output times) when the caller has them; otherwise the solve is run here.  ``debug``: also returns
+    a dict with the replay's ``exit_iters`` int32 [n_steps,4], ``stage_k`` [n_steps,4,B,C] and the
+    ``states``."""
+    act = _act(dyn)
+    for name, t in (("g_y", g_y), ("x_feat", x_feat), ("h0", h0)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a tensor")
+    dev = h0.device
+    B = h0.shape[0]
+    if B < 1 or B > L.FIODE_ODEINT_MAX_BATCH:
+        raise ValueError(f"batch {B}: needs 1 .. FIODE_ODEINT_MAX_BATCH")
+    h0 = _need(h0, "h0", (B, C), torch.float32, dev)
+    g_y = _need(g_y, "g_y", (B, C), torch.float32, dev)
+    x_feat = _need(x_feat, "x_feat", (B, X), torch.float32, dev)
+    grid = rk4_grid(t0, t1, step_size)
+    n_steps = len(grid) - 1
+    if states is None:
+        states, stats, _ = odeint_dyn(x_feat, h0, torch.from_numpy(grid).to(dev), weights, dyn, method="rk4",
+                                      step_size=float(step_size))
+    states = _need(states, "states", (n_steps + 1, B, C), torch.float32, dev)
+    ws_w, cw = _weights_c(weights, dev)
+    g_h0 = torch.empty((B, C), dtype=torch.float32, device=dev)
+    g_x = torch.empty((B, X), dtype=torch.float32, device=dev)
+    dbg = {}
+    if debug:
+        dbg = {"exit_iters": torch.empty((n_steps, 4), dtype=torch.int32, device=dev),
+               "stage_k": torch.empty((n_steps, 4, B, C), dtype=torch.float32, device=dev), "states": states}
+    lib = L.lib()
+    ws = _Workspace.get(dev, lib.fiode_odeint_backward_x_workspace_bytes(B, float(t0), float(t1), float(step_size)),
+                        "odebx")
+    dc = dyn.to_c()
+    rc = lib.fiode_odeint_backward_x(_stream(dev), ct.byref(dc), ct.byref(cw), B, float(t0), float(t1),
+                                     float(step_size), x_feat.data_ptr(), states.data_ptr(), g_y.data_ptr(),
+                                     g_h0.data_ptr(), g_x.data_ptr(), _ptr(dbg.get("exit_iters")),
+                                     _ptr(dbg.get("stage_k")), ws.data_ptr(), ws.numel(), act)
+    L.check(rc, "fiode_odeint_backward_x")
+    del ws_w
+    return (g_h0, g_x, dbg) if debug else (g_h0, g_x)
+
+
 def odetrain_config(B: int, t0: float, t1: float, step_size: float, dropout_mode: int, seed: int = 0,
                     offset: int = 0, method: str = "rk4", rtol: float = 1e-3, atol: float = 1e-3,
                     max_attempts: int = 64) -> L.OdeTrainConfig:

@@ -240,6 +240,26 @@ FIODE_API int fiode_odeint_act(void* stream, const fiode_ode_config* cfg, const 
                                const double* times, float* solution, int32_t* stats, double* dstats,
                                void* workspace, size_t workspace_bytes, int32_t activation);
 
+/* Input gradients of the eval-mode FIODE_ODE_RK4 solve above (for attacks on the image: no weight
+ * gradients).  Given g_y [B][C] = d L / d y(t1) it writes g_h0 [B][C] = d L / d h0 and g_x_feat
+ * [B][X] = d L / d x_feat.  states [n_steps + 1][B][C]: the solve's step states, i.e. the solution
+ * of fiode_odeint_act asked for its own float32 grid t_k = k step_size + t0 (the last one t1) as
+ * output times, n_steps = fiode_odeint_backward_x_steps() (ceil((t1 - t0) / step_size + 1) - 1 in
+ * float32, at most 1024; -1: invalid).  The stages are replayed from the states, four passes (one
+ * per RK4 stage over all steps) with the QP's exit taken per step's B rows as in the solve, and one
+ * wave per 32-row tile then sweeps the steps backwards; nothing is exchanged between workgroups.
+ * exit_iters (nullable, int32 [n_steps][4]) and stage_k (nullable, [n_steps][4][B][C]) receive the
+ * replay's QP exit iterations and stage derivatives.  Both activations.  Argument checks run
+ * before the workspace-size check and nothing is launched on an error; new symbols only, so
+ * FIODE_ABI_VERSION does not move. */
+FIODE_API int32_t fiode_odeint_backward_x_steps(double t0, double t1, double step_size);
+FIODE_API size_t fiode_odeint_backward_x_workspace_bytes(int32_t batch, double t0, double t1, double step_size);
+FIODE_API int fiode_odeint_backward_x(void* stream, const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
+                                      int32_t batch, double t0, double t1, double step_size, const float* x_feat,
+                                      const float* states, const float* g_y, float* g_h0, float* g_x_feat,
+                                      int32_t* exit_iters, float* stage_k, void* workspace, size_t workspace_bytes,
+                                      int32_t activation);
+
 /* ---- Differentiable solve for train_ode (pl_modules.py:490-500; models.py:235-241) -----------
  * y_hat = odeint(IVP.h_dot, (h0,), [t0, t1], method, ...) with the dynamics in TRAIN mode (fresh
  * dropout masks per func() call), backpropagated directly through the solve (use_adjoint False):
