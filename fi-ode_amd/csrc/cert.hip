@@ -446,7 +446,7 @@ extern "C" int fiode_certify_act(void* stream, const fiode_certify_config* cfg, 
   if (fblocks > 8u * (uint32_t)ncu) fblocks = 8u * (uint32_t)ncu;      // persistent: 8 workgroups per CU
   hipLaunchKernelGGL(k_cert_final, dim3(fblocks), dim3(256), 0, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_cert_decode, dim3(1), dim3(64), 0, st, a);
+  hipLaunchKernelGGL(k_cert_decode, dim3((unsigned)((a.nb + 63) / 64)), dim3(64), 0, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
   return FIODE_OK;
 }

@@ -20,14 +20,18 @@ def _dev():
     return torch.device("cuda:0")
 
 
-@pytest.mark.parametrize("T", [4, 8, 12])
+@pytest.mark.parametrize("T", [4, 8, 12, 2, 3, 5, 7, 9, 11, 16, 20, 1])
 def test_grid_matches_construction_order(T):
+    """Even and odd T (odd T ends in db_unrank's k == 2 blocks with no rows), up to the 367,123
+    rows of T = 20; T = 1 has no rows at all and the slice is empty."""
     from fiode_amd import ops
     dev = _dev()
     g = ops.certify_grid(T, device=dev).cpu().numpy()
     ref = O.db_grid_rows(10, T)
     assert g.shape == ref.shape
     assert np.array_equal(g.astype(np.int64), ref)
+    if T == 1:
+        assert g.shape == (0, 10)
 
 
 def test_grid_T40_count_and_rows():
@@ -81,3 +85,44 @@ def test_certify_driver_through_module():
     with torch.no_grad():
         ref = sum(int(int(mod(x[i:i + 1]).argmax(-1)) == int(y[i])) for i in range(3))
     assert res.correct == ref
+    _check_driver(mod, x, y, res, T=12, batches=10)
+    # 71 batches: more than one 64-thread block of k_cert_decode
+    _check_driver(mod, x, y, certify_lipschitz(mod, x, y, T=12, batches=70), T=12, batches=70)
+
+
+def _check_driver(mod, x, y, res, T, batches):
+    """The driver's figures against the per-row reference (tests/_cert_ref.py) evaluated on the
+    device's own static_state and effective weights, and its counts against the device's `out`."""
+    from fiode_amd import ops
+    from tests import _cert_ref as CR
+    dyn = mod.dyn_fun
+    dev = x.device
+    norm = mod.init_coordinates.param_map[0]
+    min_std = float(norm.std.min()) if getattr(norm, "std", None) is not None else 1.0
+    counts = O.db_grid_rows(10, T).astype(np.uint8)
+    grid = ops.certify_grid(T, device=dev)
+    certified = certified_T = 0
+    with torch.no_grad():
+        w = {k: v.detach().float().contiguous() for k, v in dyn.effective_weights().items()}
+        dc = dyn.dyn_cfg()
+        dc.dropout = 0.0
+        P = O.DynParams(**{k: w[k].cpu().numpy() for k in ops.WEIGHT_KEYS})
+        cfg = O.DynConfig(alpha_1=dc.alpha_1, alpha_2=dc.alpha_2, sigma_1=dc.sigma_1, scale_nominal=dc.scale_nominal,
+                          dropout=0.0, qp_max_iter=dc.qp_max_iter, qp_tol=dc.qp_tol)
+        assert len(res.max_violations) == x.shape[0]
+        for i in range(x.shape[0]):
+            static_state, _ = mod.init_coordinates(x[i:i + 1], dyn)
+            xf = static_state.float().reshape(-1)
+            out, _ = ops.certify_image(xf, int(y[i]), grid, w, dc, T=T, batches=batches, min_std=min_std)
+            o = out.cpu().numpy()
+            ref = CR.cert_rows(counts, int(y[i]), xf.cpu().numpy(), P, cfg, T, batches,
+                               activation=dc.activation.lower(), min_std=min_std)
+            assert o.shape == ref.out.shape and np.isfinite(o).all()
+            err = abs(res.max_violations[i] - float(ref.vmax.max()))
+            print(f"driver batches={batches} image {i}: max violation {res.max_violations[i]:.6f} "
+                  f"reference {float(ref.vmax.max()):.6f} err {err:.3e}")
+            assert err <= 2e-3, (i, res.max_violations[i], float(ref.vmax.max()))
+            assert float(np.abs(o - ref.out).max()) <= 2e-3
+            certified += int(float(o[:, 0].max()) < 0)
+            certified_T += int(float(o[:, 1].max()) < 0)
+    assert res.certified == certified == len(res.certified_idx) and res.certified_larger_T == certified_T
