@@ -129,6 +129,17 @@ class CertifyConfig(ct.Structure):
                 ("eps", ct.c_float), ("min_std", ct.c_float)]
 
 
+class CrownConfig(ct.Structure):
+    """fiode_crown_config (include/fiode.h)."""
+    _fields_ = [("n_classes", ct.c_int32), ("T", ct.c_int32), ("batches", ct.c_int32), ("label", ct.c_int32),
+                ("eps", ct.c_float), ("min_std", ct.c_float), ("stop_on_violation", ct.c_int32)]
+
+
+class CrownDebug(ct.Structure):
+    """fiode_crown_debug: optional per-row outputs of fiode_certify_crown (NULL = not written)."""
+    _fields_ = [(n, ct.c_void_p) for n in ("lb", "ub", "f_lb", "f_ub", "l2", "u2")]
+
+
 def _load():
     if not LIB_PATH.exists():
         raise FiodeLibraryError(
@@ -172,6 +183,10 @@ def _load():
         "fiode_certify_act": (ct.c_int, [_vp, ct.POINTER(CertifyConfig), ct.POINTER(DynConfig),
                                          ct.POINTER(DynWeights), _vp, _vp, ct.c_int64, _vp, _vp, _vp, ct.c_size_t,
                                          ct.c_int32]),
+        "fiode_certify_crown_workspace_bytes": (ct.c_size_t, [ct.c_int64, ct.c_int32]),
+        "fiode_certify_crown": (ct.c_int, [_vp, ct.POINTER(CrownConfig), ct.POINTER(DynConfig),
+                                           ct.POINTER(DynWeights), _vp, _vp, ct.c_int64, _vp, _vp, _vp,
+                                           ct.POINTER(CrownDebug), _vp, ct.c_size_t, ct.c_int32]),
         "fiode_odetrain_evals": (ct.c_int32, [ct.POINTER(OdeTrainConfig)]),
         "fiode_odetrain_saved_offsets": (ct.c_int, [ct.POINTER(OdeTrainConfig), _vp]),
         "fiode_odetrain_workspace_bytes": (ct.c_size_t, [ct.POINTER(OdeTrainConfig)]),

@@ -1,4 +1,5 @@
-"""Lipschitz certification driver (robustness/certify_lipschitz.py:44-163) on the HIP kernels.
+"""Certification drivers on the HIP kernels: Lipschitz (robustness/certify_lipschitz.py:44-163) and
+CROWN (robustness/certify_crown.py:36-172, ``certify_crown`` below).
 
 ``certify_lipschitz`` keeps the reference loop's semantics per image (init_coordinates -> the
 label's decision-boundary grid in ``batches`` slices -> max violation per slice -> certified iff
@@ -106,6 +107,73 @@ def certify_lipschitz(module, images: torch.Tensor, labels: torch.Tensor, T: int
                 res.certified_idx.append(int(i))
             if vtmax < 0:
                 res.certified_larger_T += 1
+    return res
+
+
+def certify_crown(module, images: torch.Tensor, labels: torch.Tensor, T: int = 40, batches: int = 400,
+                  eps: float = 0.141, grid: Optional[torch.Tensor] = None, indices=None) -> CertifyResult:
+    """certify_crown.py:121-170 for the given images (module in eval mode): CROWN bounds of the dynamics
+    over the box of half-width 1/T around every grid row, the interval QP helpers, and an image is
+    certified iff it is classified correctly and no batch maximum of Vdot + kappa is > 0.
+
+    The reference's two early-outs happen on the device: the stop flag of an image starts as
+    (argmax != label) of the validation solve, which runs on the side stream, and the first violating
+    batch sets it, so a misclassified image costs no certification work and a violated one stops at its
+    first violating batch -- with no host read between images.  ``certified_larger_T`` stays 0 (the
+    CROWN script has no such variant); ``max_violations`` holds the maximum over the batches that ran
+    (-inf for a skipped image)."""
+    dyn = module.dyn_fun
+    if getattr(dyn, "activation_name", "ReLU") != "ReLU":
+        raise NotImplementedError("certify_crown: the CROWN relaxation is implemented for activation='ReLU' only "
+                                  "(GroupSort CROWN is out of scope); use certify_lipschitz")
+    dev = images.device
+    if grid is None:
+        grid = ops.certify_grid(T, device=dev)
+    norm = module.init_coordinates.param_map[0]
+    min_std = float(norm.std.min()) if getattr(norm, "std", None) is not None else 1.0
+    res = CertifyResult()
+    module.eval()
+    idx = list(range(images.shape[0]) if indices is None else indices)
+    labels_h = labels.detach().cpu() if labels.is_cuda else labels       # one host read for all labels
+    main = torch.cuda.current_stream(dev)
+    side = shared(dev, "certify")
+    pending = []
+    with torch.no_grad():
+        w = {k: v.detach().float().contiguous() for k, v in dyn.effective_weights().items()}
+        cfg = dyn.dyn_cfg()
+        cfg.dropout = 0.0
+        ts = torch.linspace(0.0, module.t_max, 2, device=dev)
+        for i in idx:
+            image = images[i:i + 1]
+            label = int(labels_h[i])
+            static_state, state = module.init_coordinates(image, dyn)
+            feats = torch.cuda.Event()
+            feats.record(main)
+            side.wait_event(feats)
+            _record_stream((static_state, state), side)
+            with torch.cuda.stream(side):
+                sol = module.model.integrate_from(static_state, state, ts=ts, int_params=module.val_solver_params)
+                hit = module.model.output_fun(sol)[-1].argmax(-1) == label
+                flag = (~hit).to(torch.int32).reshape(1).contiguous()
+                solved = torch.cuda.Event()
+                solved.record(side)
+            hit.record_stream(main)
+            flag.record_stream(main)
+            main.wait_event(solved)               # the flag gates this image's kernels, on the device
+            out, _ = ops.certify_crown_image(static_state.float().reshape(-1), label, grid, w, cfg, T=T,
+                                             batches=batches, eps=eps, min_std=min_std, stop_on_violation=True,
+                                             stop_flag=flag)
+            pending.append((i, out, hit))
+        main.wait_stream(side)
+        for i, out, hit in pending:
+            vmax = float(out.cpu().max())
+            ok = bool(hit.item())
+            res.n_images += 1
+            res.correct += int(ok)
+            res.max_violations.append(vmax)
+            if ok and not vmax > 0:
+                res.certified += 1
+                res.certified_idx.append(int(i))
     return res
 
 

@@ -655,6 +655,49 @@ def certify_image(x_feat: torch.Tensor, label: int, grid: torch.Tensor, weights:
     return out, it
 
 
+CROWN_DEBUG_FIELDS = (("lb", C), ("ub", C), ("f_lb", C), ("f_ub", C), ("l2", M), ("u2", M))
+
+
+def certify_crown_image(x_feat: torch.Tensor, label: int, grid: torch.Tensor, weights: Dict[str, torch.Tensor],
+                        dyn: DynCfg, T: int = 40, batches: int = 400, eps: float = 0.141, min_std: float = 0.225,
+                        stop_on_violation: bool = False, stop_flag: Optional[torch.Tensor] = None,
+                        debug: bool = False):
+    """One image of certify_crown.py:129-153 (fiode_certify_crown): returns (out [nb] = per-batch max
+    violation, exit_iters [nb][2] = exits of the lower- and the upper-bound solver call) on the device,
+    and with ``debug`` a dict of the per-row arrays lb, ub, f_lb, f_ub [G][10], l2, u2 [G][128] as third
+    result.  ``stop_flag``: a device int32 tensor of one element, read and written by the kernels (nonzero
+    on entry: out is all -inf and exit_iters is left as it was, zeros here)."""
+    act = _act(dyn)
+    if act != L.FIODE_ACT_RELU:
+        raise NotImplementedError("certify_crown_image: the CROWN relaxation is implemented for activation='ReLU' only")
+    dev = grid.device
+    G = grid.shape[0]
+    x_feat = _need(x_feat.reshape(-1), "x_feat", (X,), torch.float32, dev)
+    grid = _need(grid, "grid", (G, C), torch.uint8, dev)
+    if stop_flag is not None:
+        _need(stop_flag, "stop_flag", (1,), torch.int32, dev)
+        if not stop_flag.is_contiguous():
+            raise ValueError("stop_flag: must be contiguous (the kernels write it)")
+    nb = batches + (1 if G % batches else 0)
+    out = torch.empty(nb, dtype=torch.float32, device=dev)
+    it = torch.zeros((nb, 2), dtype=torch.int32, device=dev)
+    dbg_t, dbg_c = None, None
+    if debug:
+        dbg_t = {n: torch.full((G, w), float("nan"), dtype=torch.float32, device=dev) for n, w in CROWN_DEBUG_FIELDS}
+        dbg_c = L.CrownDebug(*[dbg_t[n].data_ptr() for n, _ in CROWN_DEBUG_FIELDS])
+    ws_w, cw = _weights_c(weights, dev)
+    lib = L.lib()
+    ws = _Workspace.get(dev, lib.fiode_certify_crown_workspace_bytes(G, batches), "crown")
+    cfg = L.CrownConfig(C, int(T), int(batches), int(label), float(eps), float(min_std), int(bool(stop_on_violation)))
+    dc = dyn.to_c()
+    rc = lib.fiode_certify_crown(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), x_feat.data_ptr(),
+                                 grid.data_ptr(), G, out.data_ptr(), it.data_ptr(), _ptr(stop_flag),
+                                 ct.byref(dbg_c) if dbg_c is not None else None, ws.data_ptr(), ws.numel(), act)
+    L.check(rc, "fiode_certify_crown")
+    del ws_w
+    return (out, it, dbg_t) if debug else (out, it)
+
+
 def batched_inverse(M: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(..., n, n) -> inverse, n <= 128, float32 or complex64 (fiode_batched_inverse).
     Valid for matrices with positive-definite Hermitian part (the Cayley I + A)."""

@@ -367,6 +367,44 @@ FIODE_API int fiode_certify_act(void* stream, const fiode_certify_config* cfg, c
                                 float* out, int32_t* exit_iters, void* workspace, size_t workspace_bytes,
                                 int32_t activation);
 
+/* ---- CROWN certification on the same grid (robustness/certify_crown.py:113-158) -------------
+ * Per batch of grid rows: backward CROWN bounds (lb, ub) of the dynamics MLP over the L-inf box of
+ * half-width 1/T around each row (ReLU, adaptive lower slope), ibp_sigmoid under scale_nominal,
+ * ibp_cbf_qp (upper=False: two solver calls over rows x 10 sub-problems, each with its own
+ * batch-global exit), violation = -f_lb[label] + max_{eta >= max eta - 2/T, != label} f_ub + kappa,
+ * kappa = sqrt(2) eps / min_std.  New symbols only: FIODE_ABI_VERSION does not move. */
+typedef struct fiode_crown_config {
+  int32_t n_classes;         /* 10                                                              */
+  int32_t T;                 /* grid density; the box half-width is 1 / T                        */
+  int32_t batches;           /* as fiode_certify_config.batches (reference: 400)                 */
+  int32_t label;
+  float eps;                 /* cfg.eps: enters kappa only                                       */
+  float min_std;
+  int32_t stop_on_violation; /* the first batch whose maximum is > 0 sets the stop flag          */
+} fiode_crown_config;
+
+/* Optional per-row outputs, indexed by grid row (NULL members are not written): the CROWN bounds
+ * lb, ub [G][10] (before ibp_sigmoid), the QP bounds f_lb, f_ub [G][10] and the layer-2
+ * pre-activation bounds l2, u2 [G][128]. */
+typedef struct fiode_crown_debug {
+  float* lb; float* ub; float* f_lb; float* f_ub; float* l2; float* u2;
+} fiode_crown_debug;
+
+FIODE_API size_t fiode_certify_crown_workspace_bytes(int64_t G, int32_t batches);
+/* One image.  out [nb]: the per-batch maximum violation; exit_iters [nb][2] (nullable): the exit
+ * iteration of the lower-bound call, then of the upper-bound call; nb = batches + (G % batches != 0).
+ * stop_flag (nullable): a device int32 read and written on the device.  Nonzero on entry: every
+ * kernel returns at once, every out[b] is -inf and exit_iters is not written.  With
+ * cfg->stop_on_violation the first batch whose maximum is > 0 sets it, and the later batches skip
+ * and report -inf (without a caller's flag a word of the workspace serves).  dbg: nullable.
+ * Every argument check, the activation included, comes before the workspace check and nothing is
+ * launched on an error; FIODE_ACT_GROUPSORT returns FIODE_ESHAPE (the relaxation is ReLU's).
+ * Ranges as fiode_certify (n = 10, T <= 64, batches <= G < 2^32); G = 0 is a no-op. */
+FIODE_API int fiode_certify_crown(void* stream, const fiode_crown_config* cfg, const fiode_dyn_config* dyn,
+                                  const fiode_dyn_weights* w, const float* x_feat, const uint8_t* grid, int64_t G,
+                                  float* out, int32_t* exit_iters, int32_t* stop_flag, const fiode_crown_debug* dbg,
+                                  void* workspace, size_t workspace_bytes, int32_t activation);
+
 /* ---- Batched inverse of the Cayley maps (classification.py:282-293 convert_cayley ->
  * cayley(): (I + A)^-1 with A = U - U^H + V^H V; replaces torch.inverse / torch.linalg.inv) ---- */
 #define FIODE_DTYPE_F32 0
