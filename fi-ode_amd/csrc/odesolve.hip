@@ -20,6 +20,8 @@
 // Per-row solver state (y, the stage derivatives k_j, the dense-output coefficients) lives in the
 // workspace and is written only by the row's owner lane (wave 0, q = 0); every wave reads it after
 // a workgroup barrier.  The step controller runs redundantly (and identically) in every thread.
+// fiode_odeint_act_log: the accept branch of dopri5 also stores (t_n, dt_n) and y_n of the accepted
+// step, what the backward of odebwd.hip needs; without a log nothing else differs.
 #include "common.h"
 #include "tile.h"
 #include "tile16.h"
@@ -48,6 +50,10 @@ struct OsArgs {
   int32_t* stats;                // [8]: nfe, n_accept, n_reject, status, last exit iter, n_steps, workgroups,
                                  //      tiles per workgroup
   double* dstats;                // [4]: final dt, t reached, last error ratio
+  // step log of dopri5 (fiode_odeint_act_log; both null: no log)
+  int log_cap;
+  double* log_times;             // [log_cap][2]: t_n, dt_n of accepted step n
+  float* log_states;             // [log_cap][B][C]: y_n at the start of accepted step n
   // workspace
   float* u;                      // [B][M]
   float* y;                      // [B][C]
@@ -470,7 +476,7 @@ __device__ void os_dopri5(const OsArgs& a, const float* Q2s, const float* Q3s, O
   double dt = (double)fminf(100.0f * h0, h1);
   double tcur = a.times[0], tprev = tcur, tnext = tcur;
   float ratio = 0.f;
-  int nsteps = 0;
+  int nsteps = 0, nacc = 0;
   for (int ti = 1; ti < a.n_times; ++ti) {
     const double tout = a.times[ti];
     while (tout > tnext) {
@@ -515,10 +521,16 @@ __device__ void os_dopri5(const OsArgs& a, const float* Q2s, const float* Q3s, O
       ratio = rms_from_sum(ps[0], BC);
       const bool accept = ratio <= 1.0f;
       if (accept) {
+        const bool logged = a.log_states && nacc < a.log_cap;   // uniform; a step past the capacity is not written
+        if (logged && blockIdx.x == 0 && threadIdx.x == 0) {
+          a.log_times[2 * nacc] = tcur;
+          a.log_times[2 * nacc + 1] = dt;
+        }
         for_own_rows(a, [&](int b) {
           const int t = b / TR - blockIdx.x * a.T;
           float y0[C], acc[C], fa[C], fb[C];
           load_row10(a.y + (size_t)b * C, y0);
+          if (logged) store_row10(a.log_states + ((size_t)nacc * a.B + b) * C, y0);
           load_row10(a.K + (size_t)b * C, fa);
           load_row10(a.K + 6 * BC + (size_t)b * C, fb);
 #pragma unroll
@@ -550,6 +562,7 @@ __device__ void os_dopri5(const OsArgs& a, const float* Q2s, const float* Q3s, O
         tprev = tcur;
         tnext = tcur + dt;
         tcur = tcur + dt;
+        ++nacc;
       }
       if (blockIdx.x == 0 && threadIdx.x == 0) a.stats[accept ? 1 : 2] += 1;
       // _optimal_step_size (float64)
@@ -686,11 +699,14 @@ extern "C" size_t fiode_odeint_workspace_bytes(int32_t batch) {
   return os_layout(batch).total;
 }
 
-extern "C" int fiode_odeint_act(void* stream, const fiode_ode_config* cfg, const fiode_dyn_config* dyn,
-                                const fiode_dyn_weights* w, const float* x_feat, const float* h0,
-                                const double* times, float* solution, int32_t* stats, double* dstats,
-                                void* workspace, size_t workspace_bytes, int32_t activation) {
+extern "C" int fiode_odeint_act_log(void* stream, const fiode_ode_config* cfg, const fiode_dyn_config* dyn,
+                                    const fiode_dyn_weights* w, const float* x_feat, const float* h0,
+                                    const double* times, float* solution, int32_t* stats, double* dstats,
+                                    void* workspace, size_t workspace_bytes, int32_t activation, int32_t log_capacity,
+                                    double* step_times, float* step_states) {
   if (!cfg || !dyn || !w) return FIODE_EINVAL;
+  if ((step_times == nullptr) != (step_states == nullptr)) return FIODE_EINVAL;
+  if (step_times && (log_capacity < 1 || log_capacity > FIODE_ODEINT_LOG_MAX_STEPS)) return FIODE_EINVAL;
   if (activation != FIODE_ACT_RELU && activation != FIODE_ACT_GROUPSORT) return FIODE_EINVAL;
   const bool gs = activation == FIODE_ACT_GROUPSORT;
   if (dyn->n_hidden != C || dyn->mlp_size != M || dyn->x_dim != FIODE_X) return FIODE_ESHAPE;
@@ -711,6 +727,7 @@ extern "C" int fiode_odeint_act(void* stream, const fiode_ode_config* cfg, const
   a.x_feat = x_feat; a.h0 = h0; a.times = times;
   a.Q1 = w->Q1; a.b1 = w->b1; a.Qx = w->Qx; a.bx = w->bx; a.Q2 = w->Q2; a.b2 = w->b2; a.Q3 = w->Q3; a.b3 = w->b3;
   a.sol = solution; a.stats = stats; a.dstats = dstats;
+  a.log_cap = step_times ? log_capacity : 0; a.log_times = step_times; a.log_states = step_states;
   a.drop_block = fiode_internal::debug_drop_publish();
   // tiles -> workgroups: one tile per workgroup while they fit the resident capacity, else T each
   a.ntiles = (a.B + TR - 1) / TR;
@@ -735,6 +752,14 @@ extern "C" int fiode_odeint_act(void* stream, const fiode_ode_config* cfg, const
   else hipLaunchKernelGGL(k_ode_tiles<RELU>, dim3(grid), dim3(256), os_lds_bytes(a.T), st, a);
   FIODE_HIP_CHECK(hipGetLastError());
   return FIODE_OK;
+}
+
+extern "C" int fiode_odeint_act(void* stream, const fiode_ode_config* cfg, const fiode_dyn_config* dyn,
+                                const fiode_dyn_weights* w, const float* x_feat, const float* h0,
+                                const double* times, float* solution, int32_t* stats, double* dstats,
+                                void* workspace, size_t workspace_bytes, int32_t activation) {
+  return fiode_odeint_act_log(stream, cfg, dyn, w, x_feat, h0, times, solution, stats, dstats, workspace,
+                              workspace_bytes, activation, 0, nullptr, nullptr);
 }
 
 extern "C" int fiode_odeint(void* stream, const fiode_ode_config* cfg, const fiode_dyn_config* dyn,

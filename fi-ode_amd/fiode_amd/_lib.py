@@ -70,6 +70,7 @@ FIODE_INV_MAX_N = 128
 FIODE_ODE_MAX_BATCH = 4096          # fiode_odetrain_*
 FIODE_ODETRAIN_MAX_ATTEMPTS = 1024  # fiode_odetrain_config.max_attempts
 FIODE_ODEINT_MAX_BATCH = 65536      # fiode_odeint (tile-parallel eval-mode solve)
+FIODE_ODEINT_LOG_MAX_STEPS = 1024   # fiode_odeint_act_log / fiode_odeint_dopri5_backward_x
 FIODE_SMALL_CAYLEY_MAX_K, FIODE_SMALL_CAYLEY_MAX_RK = 16, 8192
 
 
@@ -170,6 +171,13 @@ def _load():
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, ct.c_size_t]),
         "fiode_odeint_act": (ct.c_int, [_vp, ct.POINTER(OdeConfig), ct.POINTER(DynConfig), ct.POINTER(DynWeights),
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, ct.c_size_t, ct.c_int32]),
+        "fiode_odeint_act_log": (ct.c_int, [_vp, ct.POINTER(OdeConfig), ct.POINTER(DynConfig), ct.POINTER(DynWeights),
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, ct.c_size_t, ct.c_int32, ct.c_int32,
+                                            _vp, _vp]),
+        "fiode_odeint_dopri5_backward_x_workspace_bytes": (ct.c_size_t, [ct.c_int32, ct.c_int32]),
+        "fiode_odeint_dopri5_backward_x": (ct.c_int, [_vp, ct.POINTER(DynConfig), ct.POINTER(DynWeights), ct.c_int32,
+                                                      ct.c_int32, ct.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                      _vp, _vp, ct.c_size_t, ct.c_int32]),
         "fiode_odeint_backward_x_steps": (ct.c_int32, [ct.c_double, ct.c_double, ct.c_double]),
         "fiode_odeint_backward_x_workspace_bytes": (ct.c_size_t, [ct.c_int32, ct.c_double, ct.c_double, ct.c_double]),
         "fiode_odeint_backward_x": (ct.c_int, [_vp, ct.POINTER(DynConfig), ct.POINTER(DynWeights), ct.c_int32,

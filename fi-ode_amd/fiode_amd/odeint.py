@@ -10,8 +10,11 @@ algorithms as plain torch ops on whatever device its tensors live on.
 The native solve runs without grad.  With grad enabled, ``h0`` or the static features requiring grad
 and no parameter of the dynamics requiring grad (``fiode_amd.lyapunov.no_param_grad``: an attack on
 the image), it is differentiable in its inputs: rk4 through ``fiode_odeint_backward_x``, dopri5 with
-ReLU through the train_ode dopri5 solve with dropout off, anything else through the torch steppers
-over the differentiable ``eval_dot`` (``_odeint_native_input_grad``).
+ReLU, a constant ``h0`` and a batch the train_ode solve takes through that solve with dropout off,
+every other dopri5 solve over [t0, t1] through the native solve with a log of its accepted steps and
+``fiode_odeint_dopri5_backward_x`` (the gradient on the accepted steps, their sizes held fixed: what
+the torch stepper defines), anything else through the torch steppers over the differentiable
+``eval_dot`` (``_odeint_native_input_grad``).
 
 make_solver_params (pl_modules.py:24-35) is reproduced: adaptive solvers take rtol=atol=tol;
 fixed-grid solvers take options.step_size = tol.
@@ -180,14 +183,77 @@ class _OdeintDopri5XFn(torch.autograd.Function):
         return (None, None, None, g_x) + (None,) * len(ws)
 
 
+# The native dopri5 route below (GroupSort; ReLU with h0 requiring grad or a batch past the train_ode
+# solve's).  False puts the torch stepper back for those solves (tests, timing).
+DOPRI5_NATIVE_INPUT_GRAD = True
+DOPRI5_LOG_BYTES = 1 << 28      # budget of the step log: capacity = budget / (B x 40 bytes), 8 .. 128 steps
+
+
+def dopri5_log_capacity(B: int) -> int:
+    """Accepted steps the log of a B-row solve holds (tol 1e-3 over [0, 1] takes 6-7)."""
+    return max(8, min(128, DOPRI5_LOG_BYTES // (max(int(B), 1) * 40)))
+
+
+class _Dopri5LogOverflow(RuntimeError):
+    """The solve accepted more steps than its log holds: the caller takes the torch stepper."""
+
+
+class _OdeintDopri5LogXFn(torch.autograd.Function):
+    """y(t1) of the eval-mode dopri5 solve over (h0, static_state), both activations.  Forward: the
+    native solve with the log of its accepted steps (fiode_odeint_act_log); y(t1) is the no-grad
+    solve's, bit for bit.  Backward: ``ops.odeint_dopri5_backward_x``, the adjoint of the accepted
+    steps with their sizes held fixed -- the gradient the torch stepper defines, whose error ratio is a
+    Python float.  The solve's one host read (its stats) also gives the number of accepted steps."""
+
+    @staticmethod
+    def forward(ctx, dyn_mod, plan, h0, x, *ws):
+        from . import ops
+        w = dict(zip(ops.WEIGHT_KEYS, ws))
+        times = torch.tensor([plan["t0"], plan["t1"]], dtype=torch.float64, device=h0.device)
+        sol, stats, dstats, step_times, step_states = ops.odeint_dyn(
+            x, h0, times, w, plan["dyn"], method="dopri5", rtol=plan["rtol"], atol=plan["atol"],
+            max_steps=plan["max_steps"], log_steps=plan["capacity"])
+        dyn_mod.last_solve_stats = (stats, dstats)
+        host = stats.cpu()            # the solve's one host read: status and n_accept
+        _check_solve_status(host, dstats)
+        n_steps = int(host[1])
+        if n_steps < 1 or n_steps > plan["capacity"]:
+            raise _Dopri5LogOverflow(n_steps)
+        ctx.save_for_backward(step_times, step_states, x, *ws)
+        ctx.plan, ctx.n_steps = plan, n_steps
+        return sol[-1].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            raise RuntimeError(_ONCE)
+        return _OdeintDopri5LogXFn._vjp(ctx, g)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def _vjp(ctx, g):
+        from . import ops
+        step_times, step_states, x, *ws = ctx.saved_tensors
+        p = ctx.plan
+        g_h0, g_x = ops.odeint_dopri5_backward_x(g.contiguous().float(), x, dict(zip(ops.WEIGHT_KEYS, ws)), p["dyn"],
+                                                 t1=p["t1"], step_times=step_times, step_states=step_states,
+                                                 n_steps=ctx.n_steps)
+        return (None, None, g_h0, g_x) + (None,) * len(ws)
+
+
 def _odeint_native_input_grad(dyn, h0, t, rtol, atol, method, options):
     """The routes of a solve whose inputs, and only they, require grad:
       rk4, outputs [t0, t1]:          native solve + fiode_odeint_backward_x (both activations);
-      dopri5, ReLU, outputs [t0, t1]: the train_ode dopri5 solve with dropout off + its backward_x
-                                      (d/d static_state; an h0 that requires grad goes the torch way);
-      anything else (dopri5 with GroupSort, more output times): the torch steppers over the
-      differentiable eval_dot -- correct and slow (one forward and one backward launch chain per
-      evaluation)."""
+      dopri5, ReLU, outputs [t0, t1], h0 without grad, B <= FIODE_ODE_MAX_BATCH: the train_ode dopri5
+                                      solve with dropout off + its backward_x (d/d static_state, through
+                                      the step controller);
+      every other dopri5 solve with outputs [t0, t1] (GroupSort; ReLU with h0 requiring grad or a
+                                      larger batch): native solve with the step log +
+                                      fiode_odeint_dopri5_backward_x, the gradient on the accepted
+                                      steps (DOPRI5_NATIVE_INPUT_GRAD; a solve that accepts more steps
+                                      than dopri5_log_capacity(B) takes the next route);
+      anything else (more output times): the torch steppers over the differentiable eval_dot -- correct
+      and slow (one forward and one backward launch chain per evaluation)."""
     from . import ops
     from . import _lib as L
     x = dyn.static_state
@@ -209,12 +275,23 @@ def _odeint_native_input_grad(dyn, h0, t, rtol, atol, method, options):
                                    max_attempts=int(options.get("max_attempts", ops.odetrain_default_attempts(B))))
         plan = dict(dyn=cfg, cfg=ocfg)
         fn = _OdeintDopri5XFn
-    if fn is None:
+    elif method == "dopri5" and end_points and DOPRI5_NATIVE_INPUT_GRAD and B <= L.FIODE_ODEINT_MAX_BATCH:
+        plan = dict(dyn=cfg, t0=float(t[0]), t1=float(t[-1]), rtol=float(rtol), atol=float(atol),
+                    max_steps=int(options.get("max_num_steps", 100000)), capacity=dopri5_log_capacity(B))
+        fn = _OdeintDopri5LogXFn
+
+    def torch_route():
         return _odeint_torch(lambda tt, yy: dyn._eval(yy, x), h0.float(), t, rtol, atol, method, options)
+
+    if fn is None:
+        return torch_route()
     with torch.no_grad():
         ew = dyn.effective_weights()
         w = [ew[k].detach().float().contiguous() for k in ops.WEIGHT_KEYS]
-    y = fn.apply(dyn, plan, h0.float().contiguous(), x.float().contiguous(), *w)
+    try:
+        y = fn.apply(dyn, plan, h0.float().contiguous(), x.float().contiguous(), *w)
+    except _Dopri5LogOverflow:
+        return torch_route()
     return torch.stack([h0.float(), y])
 
 

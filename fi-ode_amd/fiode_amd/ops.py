@@ -355,14 +355,20 @@ def dyn_eval_backward(g_f: torch.Tensor, h: torch.Tensor, x_feat: torch.Tensor, 
 
 def odeint_dyn(x_feat: torch.Tensor, h0: torch.Tensor, times: torch.Tensor, weights: Dict[str, torch.Tensor],
                dyn: DynCfg, method: str = "dopri5", rtol: float = 1e-3, atol: float = 1e-3,
-               step_size: Optional[float] = None, max_steps: int = 100000):
+               step_size: Optional[float] = None, max_steps: int = 100000, log_steps: int = 0):
     """fiode_odeint: solve dh/dt = eval_dot(h, x_feat) (eval mode) from h0 over ``times``.
-    Returns (solution [T,B,C], stats int32[8], dstats float64[4]) -- all on the device."""
+    Returns (solution [T,B,C], stats int32[8], dstats float64[4]) -- all on the device.
+    ``log_steps`` > 0 (fiode_odeint_act_log, dopri5): also returns (step_times float64 [log_steps,2],
+    step_states [log_steps,B,C]), the (t_n, dt_n) and y_n of the accepted steps n < min(stats[1],
+    log_steps); the solution and the stats are those of the call without a log."""
     act = _act(dyn)
     dev = h0.device
     B = h0.shape[0]
     if B > L.FIODE_ODEINT_MAX_BATCH:
         raise ValueError(f"batch {B} > FIODE_ODEINT_MAX_BATCH")
+    log_steps = int(log_steps)
+    if log_steps < 0 or log_steps > L.FIODE_ODEINT_LOG_MAX_STEPS:
+        raise ValueError(f"log_steps {log_steps}: needs 0 .. FIODE_ODEINT_LOG_MAX_STEPS")
     h0 = _need(h0, "h0", (B, C), torch.float32, dev)
     x_feat = _need(x_feat, "x_feat", (B, X), torch.float32, dev)
     T = times.shape[0]
@@ -383,6 +389,16 @@ def odeint_dyn(x_feat: torch.Tensor, h0: torch.Tensor, times: torch.Tensor, weig
     lib = L.lib()
     ws = _Workspace.get(dev, lib.fiode_odeint_workspace_bytes(B), "ode")
     dc = dyn.to_c()
+    if log_steps:
+        step_times = torch.zeros((log_steps, 2), dtype=torch.float64, device=dev)
+        step_states = torch.empty((log_steps, B, C), dtype=torch.float32, device=dev)
+        rc = lib.fiode_odeint_act_log(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), x_feat.data_ptr(),
+                                      h0.data_ptr(), times.data_ptr(), sol.data_ptr(), stats.data_ptr(),
+                                      dstats.data_ptr(), ws.data_ptr(), ws.numel(), act, log_steps,
+                                      step_times.data_ptr(), step_states.data_ptr())
+        L.check(rc, "fiode_odeint_act_log")
+        del ws_w
+        return sol, stats, dstats, step_times, step_states
     rc = lib.fiode_odeint_act(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), x_feat.data_ptr(),
                               h0.data_ptr(), times.data_ptr(), sol.data_ptr(), stats.data_ptr(), dstats.data_ptr(),
                               ws.data_ptr(), ws.numel(), act)
@@ -448,6 +464,53 @@ def odeint_backward_x(g_y: torch.Tensor, x_feat: torch.Tensor, h0: torch.Tensor,
                                      g_h0.data_ptr(), g_x.data_ptr(), _ptr(dbg.get("exit_iters")),
                                      _ptr(dbg.get("stage_k")), ws.data_ptr(), ws.numel(), act)
     L.check(rc, "fiode_odeint_backward_x")
+    del ws_w
+    return (g_h0, g_x, dbg) if debug else (g_h0, g_x)
+
+
+def odeint_dopri5_backward_x(g_y: torch.Tensor, x_feat: torch.Tensor, weights: Dict[str, torch.Tensor], dyn: DynCfg,
+                             *, t1: float, step_times: torch.Tensor, step_states: torch.Tensor, n_steps: int,
+                             debug: bool = False):
+    """fiode_odeint_dopri5_backward_x: for the eval-mode dopri5 solve y(t1) = odeint(h_dot, h0, [t0, t1])
+    and ``g_y`` [B,C] = dL/dy(t1), returns (g_h0 [B,C], g_x_feat [B,X]): the gradient on the accepted
+    steps with their sizes held fixed.  ``step_times`` / ``step_states``: the log ``odeint_dyn(...,
+    log_steps=...)`` returned (at least ``n_steps`` entries), ``n_steps`` its stats[1] as a host integer.
+    ``debug``: also returns a dict with the replay's ``exit_iters`` int32 [n_steps,7] and ``stage_k``
+    [n_steps,7,B,C] (entry 6, k7, for the last step only: -1 / zeros elsewhere)."""
+    act = _act(dyn)
+    for name, t in (("g_y", g_y), ("x_feat", x_feat), ("step_times", step_times), ("step_states", step_states)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: expected a tensor")
+    n_steps = int(n_steps)
+    if n_steps < 1 or n_steps > L.FIODE_ODEINT_LOG_MAX_STEPS:
+        raise ValueError(f"n_steps {n_steps}: needs 1 .. FIODE_ODEINT_LOG_MAX_STEPS")
+    dev = g_y.device
+    B = g_y.shape[0]
+    if B < 1 or B > L.FIODE_ODEINT_MAX_BATCH:
+        raise ValueError(f"batch {B}: needs 1 .. FIODE_ODEINT_MAX_BATCH")
+    if step_times.dim() != 2 or step_states.dim() != 3 or step_times.shape[0] < n_steps or step_states.shape[0] < n_steps:
+        raise ValueError(f"step log: needs at least n_steps = {n_steps} entries; got step_times "
+                         f"{tuple(step_times.shape)}, step_states {tuple(step_states.shape)}")
+    g_y = _need(g_y, "g_y", (B, C), torch.float32, dev)
+    x_feat = _need(x_feat, "x_feat", (B, X), torch.float32, dev)
+    step_times = _need(step_times, "step_times", (step_times.shape[0], 2), torch.float64, dev)
+    step_states = _need(step_states, "step_states", (step_states.shape[0], B, C), torch.float32, dev)
+    ws_w, cw = _weights_c(weights, dev)
+    g_h0 = torch.empty((B, C), dtype=torch.float32, device=dev)
+    g_x = torch.empty((B, X), dtype=torch.float32, device=dev)
+    dbg = {}
+    if debug:
+        dbg = {"exit_iters": torch.empty((n_steps, 7), dtype=torch.int32, device=dev),
+               "stage_k": torch.zeros((n_steps, 7, B, C), dtype=torch.float32, device=dev)}
+    lib = L.lib()
+    ws = _Workspace.get(dev, lib.fiode_odeint_dopri5_backward_x_workspace_bytes(B, n_steps), "odedpbx")
+    dc = dyn.to_c()
+    rc = lib.fiode_odeint_dopri5_backward_x(_stream(dev), ct.byref(dc), ct.byref(cw), B, n_steps, float(t1),
+                                            step_times.data_ptr(), step_states.data_ptr(), x_feat.data_ptr(),
+                                            g_y.data_ptr(), g_h0.data_ptr(), g_x.data_ptr(),
+                                            _ptr(dbg.get("exit_iters")), _ptr(dbg.get("stage_k")), ws.data_ptr(),
+                                            ws.numel(), act)
+    L.check(rc, "fiode_odeint_dopri5_backward_x")
     del ws_w
     return (g_h0, g_x, dbg) if debug else (g_h0, g_x)
 

@@ -240,6 +240,45 @@ FIODE_API int fiode_odeint_act(void* stream, const fiode_ode_config* cfg, const 
                                const double* times, float* solution, int32_t* stats, double* dstats,
                                void* workspace, size_t workspace_bytes, int32_t activation);
 
+/* fiode_odeint_act with a log of the FIODE_ODE_DOPRI5 solve's ACCEPTED steps, the one thing a
+ * backward cannot reconstruct.  step_times (device double [log_capacity][2]) receives (t_n, dt_n)
+ * and step_states (device float [log_capacity][B][C]) y_n at the start of accepted step n, written
+ * in the accept branch; rejected attempts leave no trace.  An accepted step with index >=
+ * log_capacity is not written, and stats[1] (n_accept) still counts it: n_accept > log_capacity
+ * tells the host that the log is incomplete.  The two pointers are both NULL (no log: exactly
+ * fiode_odeint_act) or both set with 1 <= log_capacity <= FIODE_ODEINT_LOG_MAX_STEPS
+ * (FIODE_EINVAL otherwise).  The solution, stats and dstats are bit for bit those of
+ * fiode_odeint_act: the log adds nothing to the exchange or to the evaluations, and the workspace
+ * is fiode_odeint_workspace_bytes().  FIODE_ODE_RK4 ignores the log.  A new symbol only:
+ * FIODE_ABI_VERSION does not move. */
+#define FIODE_ODEINT_LOG_MAX_STEPS 1024
+FIODE_API int fiode_odeint_act_log(void* stream, const fiode_ode_config* cfg, const fiode_dyn_config* dyn,
+                                   const fiode_dyn_weights* w, const float* x_feat, const float* h0,
+                                   const double* times, float* solution, int32_t* stats, double* dstats,
+                                   void* workspace, size_t workspace_bytes, int32_t activation,
+                                   int32_t log_capacity, double* step_times, float* step_states);
+
+/* Input gradients of the eval-mode FIODE_ODE_DOPRI5 solve over output times [t0, t1], on its
+ * accepted steps with their sizes held fixed (the step controller carries no gradient): the adjoint
+ * of the solve's float32 step expressions over the logged sequence (t_n, dt_n), n < n_steps, and of
+ * the dense output at t1 inside the last step (t_{N-1} < t1 <= t_{N-1} + dt_{N-1}).  step_times
+ * (device) and step_states are the log of fiode_odeint_act_log and n_steps its n_accept, a host
+ * integer in 1 .. FIODE_ODEINT_LOG_MAX_STEPS.  Given g_y [B][C] = d L / d y(t1) it writes g_h0
+ * [B][C] and g_x_feat [B][X]; no weight gradients.  The stages k1..k6 of all steps are replayed from
+ * the logged states, six passes over n_steps x B rows plus one over the last step's B rows for k7,
+ * with the QP's exit taken per step's B rows as in the solve; one wave per 32-row tile then sweeps
+ * the steps backwards.  Nothing is exchanged between workgroups.  exit_iters (nullable, int32
+ * [n_steps][7]) and stage_k (nullable, [n_steps][7][B][C]) receive the replay's QP exit iterations
+ * and stage derivatives; entry 6 (k7) is evaluated for the last step only (exit_iters -1, stage_k
+ * not written elsewhere).  Both activations.  Argument checks run before the workspace-size check
+ * and nothing is launched on an error.  New symbols only: FIODE_ABI_VERSION does not move. */
+FIODE_API size_t fiode_odeint_dopri5_backward_x_workspace_bytes(int32_t batch, int32_t n_steps);
+FIODE_API int fiode_odeint_dopri5_backward_x(void* stream, const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
+                                             int32_t batch, int32_t n_steps, double t1, const double* step_times,
+                                             const float* step_states, const float* x_feat, const float* g_y,
+                                             float* g_h0, float* g_x_feat, int32_t* exit_iters, float* stage_k,
+                                             void* workspace, size_t workspace_bytes, int32_t activation);
+
 /* Input gradients of the eval-mode FIODE_ODE_RK4 solve above (for attacks on the image: no weight
  * gradients).  Given g_y [B][C] = d L / d y(t1) it writes g_h0 [B][C] = d L / d h0 and g_x_feat
  * [B][X] = d L / d x_feat.  states [n_steps + 1][B][C]: the solve's step states, i.e. the solution
