@@ -250,10 +250,12 @@ __global__ __launch_bounds__(256) void k_lyap_prep(LyapArgs a) {
 // max_iter - 1 for its convergence bits, AND-ed per pass into CONV_SLOTS words (the batch-global
 // exit, barrier_projection.py:247-249).  Persistent: two workgroups per CU (LDS 72.9 KB each), the
 // weight images staged once per workgroup; with more than one tile per SIMD, one wave's QP (VALU)
-// overlaps the other's MFMA.
+// overlaps the other's MFMA.  A: the activation of the two hidden layers (tile.h; <RELU> is the
+// kernel as it was, <GROUPSORT> sorts the dropped values of both passes).
 #ifndef FWD_WAVES
 #define FWD_WAVES 4           // waves (tiles in flight) per workgroup
 #endif
+template <Act A>
 __global__ __launch_bounds__(64 * FWD_WAVES, 8 / FWD_WAVES) void k_lyap_fwd(LyapArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   LY_T0();
@@ -289,8 +291,8 @@ __global__ __launch_bounds__(64 * FWD_WAVES, 8 / FWD_WAVES) void k_lyap_fwd(Lyap
       const uint32_t kw1[4] = {kq[2 * p].x, kq[2 * p].y, kq[2 * p].z, kq[2 * p].w};
       const uint32_t kw2[4] = {kq[2 * p + 1].x, kq[2 * p + 1].y, kq[2 * p + 1].z, kq[2 * p + 1].w};
       f32x16 z1[4], z2[4];
-      const f32x16 z3 = mlp_tile(Q2s, Q3s, q1, a.u + (size_t)b * M, a.b2, a.b3, h, kw1, kw2, a.drop_scale,
-                                 col, half, z1, z2);
+      const f32x16 z3 = mlp_tile<true, A>(Q2s, Q3s, q1, a.u + (size_t)b * M, a.b2, a.b3, h, kw1, kw2, a.drop_scale,
+                                          col, half, z1, z2);
       float fp[C];
       gather_ft(z3, half, fp);
 #pragma unroll
@@ -342,6 +344,30 @@ constexpr size_t BWD_LDS = (size_t)(M + C) * LDQ * sizeof(float) + sizeof(BwdSta
 //     dQ3 columns 32w.., dQ1 rows 32w..; MFMA with K = the tile's samples); db2 / db3 ride on the
 //     A operand reads; the tile's per-image g_u partial (fixed-order sum) -> gu_tiles.
 // One partial slab per workgroup (k_lyap_reduce sums them in a fixed order).
+//
+// A = GROUPSORT: unit u pairs with unit u + 64, which in the map above lives in wave w ^ 2.  Phase B
+// therefore gives wave w the 32 units U_w = {16w .. 16w + 15} u {64 + 16w .. 64 + 16w + 15} as the
+// rows of its MFMA A operands (tile row i: unit 16w + (i & 15) + 64 (i >> 4); wave_unit).  By acc_row,
+// tile rows i and i + 16 are registers r and r + 8 of one lane, so every pair is lane-local: 8 max /
+// min per layer per lane, no exchange, no LDS round trip and no barrier more than RELU has.  The unit
+// map moves the Q2 row reads of layer 2, b2w, q3t, the Q2 column reads and the output block of g_a1,
+// the layer-1 codes and keep bits the wave routes g_a1 by (its units are registers 8 (w & 1) .. + 7
+// of z1[w >> 1] and z1[2 + (w >> 1)]: bits 8w .. 8w + 7 of the full-tile sort's codes), the layer-2
+// keep bits (16-bit halves of words w >> 1 and 2 + (w >> 1)) and the stores into st.a2 / g2 / g1 --
+// which stay in true unit order (register groups 0, 1 and 2, 3 are 16 consecutive units each: two
+// base columns), so the weight-gradient phase, the g_u partials and the slab layout read them as
+// before (st.a1: every wave holds all of a1, wave w stores block w of it).  The k-order of the
+// layer-2 accumulation is RELU's, and the forward's: d and its order codes are the forward's bits.
+__device__ __forceinline__ int wave_unit(int w, int i) { return 16 * w + (i & 15) + 64 * (i >> 4); }
+// store_acc_rows of a block in the paired unit map (register group g: units wave_unit(w, 8 g) ..)
+__device__ __forceinline__ void store_acc_rows_paired(float* base_row, int w, int half, const f32x16& z) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+    *reinterpret_cast<f32x4*>(base_row + wave_unit(w, 8 * g) + 4 * half) =
+        f32x4{z[4 * g], z[4 * g + 1], z[4 * g + 2], z[4 * g + 3]};
+}
+
+template <Act A>
 __global__ __launch_bounds__(256, 1) void k_lyap_bwd(LyapArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Q2s = smem;                         // Q2[i][k] (not transposed)
@@ -354,17 +380,27 @@ __global__ __launch_bounds__(256, 1) void k_lyap_bwd(LyapArgs a) {
   load_weight_images(a.Q2, nullptr, Q2s, nullptr);
   __syncthreads();
   LY_T(8);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, half = lane >> 5, col = lane & 31;
+  const int lane = threadIdx.x & 63, half = lane >> 5, col = lane & 31;
+  // (GROUPSORT: the wave index as a scalar, so the wave's unit offsets and its choice of a1 block cost
+  // no vector registers; RELU keeps the code it had)
+  const int w = A == GROUPSORT ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
   float q1[4][5], q3t[5];
 #pragma unroll
   for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
     for (int s = 0; s < 5; ++s) q1[mb][s] = a.Q1[(32 * mb + col) * C + 2 * s + half];
+  // (the RELU expressions below stay as they were written, so that <RELU> compiles to the kernel it was)
 #pragma unroll
-  for (int s = 0; s < 5; ++s) q3t[s] = a.Q3[(2 * s + half) * M + 32 * w + col];   // A operand of Q3^T g_ft^T, block w
+  for (int s = 0; s < 5; ++s) {              // A operand of Q3^T g_ft^T, block w
+    if constexpr (A == GROUPSORT) q3t[s] = a.Q3[(2 * s + half) * M + wave_unit(w, col)];
+    else q3t[s] = a.Q3[(2 * s + half) * M + 32 * w + col];
+  }
   f32x4 b2w[4];                              // b2 of block w in accumulator order
 #pragma unroll
-  for (int g = 0; g < 4; ++g) b2w[g] = *reinterpret_cast<const f32x4*>(a.b2 + 32 * w + 8 * g + 4 * half);
+  for (int g = 0; g < 4; ++g) {
+    if constexpr (A == GROUPSORT) b2w[g] = *reinterpret_cast<const f32x4*>(a.b2 + wave_unit(w, 8 * g) + 4 * half);
+    else b2w[g] = *reinterpret_cast<const f32x4*>(a.b2 + 32 * w + 8 * g + 4 * half);
+  }
   const float kappa = a.kappa_dev ? *a.kappa_dev : a.kappa;
   const int K0 = qp_exit_iter(conv_word(a, 0), a.d.max_iter);
   const int K1 = qp_exit_iter(conv_word(a, 1), a.d.max_iter);
@@ -477,23 +513,43 @@ __global__ __launch_bounds__(256, 1) void k_lyap_bwd(LyapArgs a) {
       // h and the keep words from phase A's LDS copy (rows past N: h = 0; their gradients are 0)
       const uint4 k1 = *reinterpret_cast<const uint4*>(&st.kw[t][col][0]);
       const uint32_t kw1[4] = {k1.x, k1.y, k1.z, k1.w};
-      const uint32_t kw2w = st.kw[t][col][4 + w];
-      // layer 1 (all units): z1 = u[b] + Q1 h, dropout-ReLU
+      // (GROUPSORT: the layer-2 keep bits of the wave's 16 units and of their partners, in bits 0..15)
+      const uint32_t kw2w = A == GROUPSORT ? st.kw[t][col][4 + (w >> 1)] >> (16 * (w & 1)) : st.kw[t][col][4 + w];
+      const uint32_t kw2p = A == GROUPSORT ? st.kw[t][col][6 + (w >> 1)] >> (16 * (w & 1)) : 0u;
+      // layer 1 (all units): z1 = u[b] + Q1 h, dropout-ReLU (GROUPSORT: dropout, then the full-tile sort)
       f32x16 z1[4] = {un[0], un[1], un[2], un[3]};
-      if (t + 1 < 4 && tile + 1 < ntiles) load_u(tile + 1);
+      if (A == RELU && t + 1 < 4 && tile + 1 < ntiles) load_u(tile + 1);
 #pragma unroll
       for (int s = 0; s < 5; ++s) {
         const float bs = st.hh[t][col][2 * s + half];
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb) z1[mb] = mfma32(q1[mb][s], bs, z1[mb]);
       }
-#pragma unroll
-      for (int mb = 0; mb < 4; ++mb) dropout_relu(z1[mb], kw1[mb], half, a.drop_scale);
+      uint32_t gt1 = 0, eq1 = 0, gt2 = 0, eq2 = 0;   // GROUPSORT: the wave's pair codes of both layers (bits 0..7)
+      uint32_t kw1w = 0, kw1p = 0;                   // and its layer-1 keep bits, as kw2w / kw2p
       f32x16 z1w;                                  // this wave's block of a1 (w is wave-uniform)
-      if (w == 0) z1w = z1[0];
-      else if (w == 1) z1w = z1[1];
-      else if (w == 2) z1w = z1[2];
-      else z1w = z1[3];
+      if constexpr (A == GROUPSORT) {
+        dropout_groupsort_tile_codes(z1, kw1, half, a.drop_scale, gt1, eq1);
+        gt1 >>= 8 * w;
+        eq1 >>= 8 * w;
+        kw1w = ((w >> 1) ? kw1[1] : kw1[0]) >> (16 * (w & 1));
+        kw1p = ((w >> 1) ? kw1[3] : kw1[2]) >> (16 * (w & 1));
+        // a1 -> LDS now, straight from the full tile (every wave holds all of a1, so the stores need
+        // not follow the paired map: wave w stores block w; the backward routes by the codes, not by
+        // a1, so no copy of the wave's block stays in registers).  The stage is free: its last
+        // readers passed the barrier that ended the previous tile.
+        if (w == 0) store_acc_rows(&st.a1[col][0], 0, half, z1[0]);
+        else if (w == 1) store_acc_rows(&st.a1[col][0], 1, half, z1[1]);
+        else if (w == 2) store_acc_rows(&st.a1[col][0], 2, half, z1[2]);
+        else store_acc_rows(&st.a1[col][0], 3, half, z1[3]);
+      } else {
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) dropout_relu(z1[mb], kw1[mb], half, a.drop_scale);
+        if (w == 0) z1w = z1[0];
+        else if (w == 1) z1w = z1[1];
+        else if (w == 2) z1w = z1[2];
+        else z1w = z1[3];
+      }
       // layer 2, block w: z2 = b2 + Q2 a1
       f32x16 z2;
 #pragma unroll
@@ -504,7 +560,8 @@ __global__ __launch_bounds__(256, 1) void k_lyap_bwd(LyapArgs a) {
       // compiler otherwise waits on every read right before its MFMA -- one wave per SIMD, nothing
       // else hides the ~100-cycle LDS latency)
       {
-        const float* q2row = Q2s + (32 * w + col) * LDQ + 4 * half;
+        const float* q2row = A == GROUPSORT ? Q2s + wave_unit(w, col) * LDQ + 4 * half
+                                            : Q2s + (32 * w + col) * LDQ + 4 * half;
         f32x4 q = *reinterpret_cast<const f32x4*>(q2row);
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) {                // kk = 4 kb + g
@@ -515,19 +572,33 @@ __global__ __launch_bounds__(256, 1) void k_lyap_bwd(LyapArgs a) {
           q = qn;
         }
       }
-      dropout_relu(z2, kw2w, half, a.drop_scale);
-      // g_a2^T block w = Q3^T g_ft^T ; g_z2 = g_a2 [a2 > 0] * scale
+      if constexpr (A == GROUPSORT) dropout_groupsort_pairs(z2, kw2w, kw2p, half, a.drop_scale, gt2, eq2);
+      else dropout_relu(z2, kw2w, half, a.drop_scale);
+      // g_a2^T block w = Q3^T g_ft^T ; g_z2 = g_a2 [a2 > 0] * scale (GROUPSORT: g_a2 routed by the
+      // order of the pair's dropped values, times keep * scale)
       f32x16 ga = f16_zero();
 #pragma unroll
       for (int s = 0; s < 5; ++s) ga = mfma32(q3t[s], st.gf[t][col][2 * s + half], ga);
+      if constexpr (A == GROUPSORT) {
+        dropout_groupsort_pairs_backward(ga, gt2, eq2, kw2w, kw2p, half, a.drop_scale);
+        store_acc_rows_paired(&st.a2[col][0], w, half, z2);
+        store_acc_rows_paired(&st.g2[col][0], w, half, ga);
+      } else {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) ga[r] = z2[r] > 0.f ? ga[r] * a.drop_scale : 0.f;
-      store_acc_rows(&st.a1[col][0], w, half, z1w);
-      store_acc_rows(&st.a2[col][0], w, half, z2);
-      store_acc_rows(&st.g2[col][0], w, half, ga);
+        for (int r = 0; r < 16; ++r) ga[r] = z2[r] > 0.f ? ga[r] * a.drop_scale : 0.f;
+        store_acc_rows(&st.a1[col][0], w, half, z1w);
+        store_acc_rows(&st.a2[col][0], w, half, z2);
+        store_acc_rows(&st.g2[col][0], w, half, ga);
+      }
       LY_T(10);
       __syncthreads();
       LY_T(11);
+      // (GROUPSORT: the next tile's u rows are fetched from here on, once the 64 registers of a1 are
+      // dead -- the sort's codes and keep bits leave no room for both; the loads still have the g_a1
+      // product and the weight-gradient phase to land.  Unconditional, so that no old value of un
+      // stays live beside a1: load_u clamps its rows, and after the round's or the batch's last tile
+      // the result is not used)
+      if (A == GROUPSORT) load_u(tile + 1);
       // g_a1^T block w = Q2^T g_z2^T: A = Q2[32kb + 8g + 4half + e][32w + col], B = g_z2[n = col][32kb + 8g + 4half + e]
       f32x16 gb = f16_zero();
       {
@@ -535,7 +606,8 @@ __global__ __launch_bounds__(256, 1) void k_lyap_bwd(LyapArgs a) {
           const int k0 = 32 * (kk >> 2) + 8 * (kk & 3) + 4 * half;
           gz = *reinterpret_cast<const f32x4*>(&st.g2[col][k0]);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) qa[e] = Q2s[(k0 + e) * LDQ + 32 * w + col];
+          for (int e = 0; e < 4; ++e)
+            qa[e] = A == GROUPSORT ? Q2s[(k0 + e) * LDQ + wave_unit(w, col)] : Q2s[(k0 + e) * LDQ + 32 * w + col];
         };
         float qa[4];
         f32x4 gz;
@@ -552,9 +624,14 @@ __global__ __launch_bounds__(256, 1) void k_lyap_bwd(LyapArgs a) {
           gz = gn;
         }
       }
+      if constexpr (A == GROUPSORT) {
+        dropout_groupsort_pairs_backward(gb, gt1, eq1, kw1w, kw1p, half, a.drop_scale);
+        store_acc_rows_paired(&st.g1[col][0], w, half, gb);
+      } else {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) gb[r] = z1w[r] > 0.f ? gb[r] * a.drop_scale : 0.f;
-      store_acc_rows(&st.g1[col][0], w, half, gb);
+        for (int r = 0; r < 16; ++r) gb[r] = z1w[r] > 0.f ? gb[r] * a.drop_scale : 0.f;
+        store_acc_rows(&st.g1[col][0], w, half, gb);
+      }
       LY_T(12);
       __syncthreads();
       LY_T(13);
@@ -1063,6 +1140,12 @@ extern "C" size_t fiode_lyap_workspace_bytes(const fiode_lyap_config* cfg, const
 extern "C" int fiode_lyap_step(void* stream, const fiode_lyap_config* cfg, const fiode_dyn_config* dyn,
                                const fiode_dyn_weights* w, const fiode_lyap_io* io, fiode_lyap_grads* grads,
                                void* workspace, size_t workspace_bytes) {
+  return fiode_lyap_step_act(stream, cfg, dyn, w, io, grads, workspace, workspace_bytes, FIODE_ACT_RELU);
+}
+
+extern "C" int fiode_lyap_step_act(void* stream, const fiode_lyap_config* cfg, const fiode_dyn_config* dyn,
+                                   const fiode_dyn_weights* w, const fiode_lyap_io* io, fiode_lyap_grads* grads,
+                                   void* workspace, size_t workspace_bytes, int32_t activation) {
   int rc = check_dyn(dyn);
   if (rc) return rc;
   if (!cfg || !w || !io || !grads || !workspace) return FIODE_EINVAL;
@@ -1078,6 +1161,8 @@ extern "C" int fiode_lyap_step(void* stream, const fiode_lyap_config* cfg, const
   if (!grads->Q1 || !grads->b1 || !grads->Qx || !grads->bx || !grads->Q2 || !grads->b2 || !grads->Q3 ||
       !grads->b3 || !grads->x_feat)
     return FIODE_EINVAL;
+  if (activation != FIODE_ACT_RELU && activation != FIODE_ACT_GROUPSORT) return FIODE_EINVAL;
+  const bool gs = activation == FIODE_ACT_GROUPSORT;
   const WsLayout L = ws_layout(B, S);
   if (workspace_bytes < L.total) return FIODE_EWORKSPACE;
   char* ws = static_cast<char*>(workspace);
@@ -1148,10 +1233,12 @@ extern "C" int fiode_lyap_step(void* stream, const fiode_lyap_config* cfg, const
   hipLaunchKernelGGL(k_lyap_prep, dim3((a.N + 255) / 256), dim3(256), 0, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
   if ((rc = mark())) return rc;
-  hipLaunchKernelGGL(k_lyap_fwd, dim3(fwd_blocks), dim3(64 * FWD_WAVES), lds_fwd, st, a);
+  if (gs) hipLaunchKernelGGL(k_lyap_fwd<GROUPSORT>, dim3(fwd_blocks), dim3(64 * FWD_WAVES), lds_fwd, st, a);
+  else hipLaunchKernelGGL(k_lyap_fwd<RELU>, dim3(fwd_blocks), dim3(64 * FWD_WAVES), lds_fwd, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
   if ((rc = mark())) return rc;
-  hipLaunchKernelGGL(k_lyap_bwd, dim3(L.nslab), dim3(256), BWD_LDS, st, a);
+  if (gs) hipLaunchKernelGGL(k_lyap_bwd<GROUPSORT>, dim3(L.nslab), dim3(256), BWD_LDS, st, a);
+  else hipLaunchKernelGGL(k_lyap_bwd<RELU>, dim3(L.nslab), dim3(256), BWD_LDS, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
   if ((rc = mark())) return rc;
   const int red_blocks = (SLAB + RED_COLS - 1) / RED_COLS + (B * M + RED_COLS - 1) / RED_COLS + 1;

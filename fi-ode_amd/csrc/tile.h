@@ -40,8 +40,9 @@ __device__ __forceinline__ void dropout_relu(f32x16& z, uint32_t kw, int half, f
 
 // The activation of the MLP's two hidden layers, a compile-time parameter of the tile code.
 // GROUPSORT (group size 2 over the halves, cayley.py GroupSort): with a = z[:M/2], b = z[M/2:] the
-// output is cat(max(a, b), min(a, b)) -- unit u pairs with unit u + M/2.  Eval mode only (no
-// dropout); the training kernels instantiate RELU.
+// output is cat(max(a, b), min(a, b)) -- unit u pairs with unit u + M/2.  With dropout (the fused
+// Lyapunov training step, lyap.hip) the sort takes the dropped values: GroupSort(dropout(z)),
+// classification.py:98,100.  The train_ode solves (odetrain.hip) instantiate RELU only.
 enum Act { RELU = 0, GROUPSORT = 1 };
 
 // GroupSort on the four accumulator blocks of a 32-row wave tile, in place.  Block mb holds units
@@ -73,6 +74,78 @@ __device__ __forceinline__ void groupsort_tile_codes(f32x16 (&z)[4], uint32_t& g
       z[mb][r] = fmaxf(a, b);
       z[mb + 2][r] = fminf(a, b);
     }
+}
+
+// GroupSort(dropout(z)) on the four accumulator blocks of a wave tile, in place: d = keep ? z * scale
+// : 0 (dropout_relu's float32 expression), then the sort of groupsort_tile.  The keep bits of the
+// pair z[mb][r] / z[mb + 2][r] are bit acc_row(r, half) of kw[mb] and of kw[mb + 2].  A pair with
+// both members dropped is a tie of two zeros.
+__device__ __forceinline__ void dropout_groupsort_tile(f32x16 (&z)[4], const uint32_t (&kw)[4], int half,
+                                                       float scale) {
+#pragma unroll
+  for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const bool ka = (kw[mb] >> acc_row(r, half)) & 1u, kb = (kw[mb + 2] >> acc_row(r, half)) & 1u;
+      const float a = ka ? z[mb][r] * scale : 0.f, b = kb ? z[mb + 2][r] * scale : 0.f;
+      z[mb][r] = fmaxf(a, b);
+      z[mb + 2][r] = fminf(a, b);
+    }
+}
+
+// dropout_groupsort_tile that also returns the order of every pair of dropped values (the codes of
+// groupsort_tile_codes; the sorted values are the same bits).
+__device__ __forceinline__ void dropout_groupsort_tile_codes(f32x16 (&z)[4], const uint32_t (&kw)[4], int half,
+                                                             float scale, uint32_t& gt, uint32_t& eq) {
+  gt = 0;
+  eq = 0;
+#pragma unroll
+  for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const bool ka = (kw[mb] >> acc_row(r, half)) & 1u, kb = (kw[mb + 2] >> acc_row(r, half)) & 1u;
+      const float a = ka ? z[mb][r] * scale : 0.f, b = kb ? z[mb + 2][r] * scale : 0.f;
+      gt |= (a > b ? 1u : 0u) << (16 * mb + r);
+      eq |= (a == b ? 1u : 0u) << (16 * mb + r);
+      z[mb][r] = fmaxf(a, b);
+      z[mb + 2][r] = fminf(a, b);
+    }
+}
+
+// The same on ONE accumulator block whose 32 rows are 16 units u and their 16 partners u + M/2 (tile
+// rows i and i + 16, i.e. registers r and r + 8 of one lane: the paired unit map of k_lyap_bwd).
+// ka / kb: the keep bits of the 16 units and of their partners, bit acc_row(r, half) for r < 8.
+// Bit r of gt / eq: d[u] > d[u + M/2] and d[u] == d[u + M/2].
+__device__ __forceinline__ void dropout_groupsort_pairs(f32x16& z, uint32_t ka, uint32_t kb, int half, float scale,
+                                                        uint32_t& gt, uint32_t& eq) {
+  gt = 0;
+  eq = 0;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const bool ba = (ka >> acc_row(r, half)) & 1u, bb = (kb >> acc_row(r, half)) & 1u;
+    const float a = ba ? z[r] * scale : 0.f, b = bb ? z[r + 8] * scale : 0.f;
+    gt |= (a > b ? 1u : 0u) << r;
+    eq |= (a == b ? 1u : 0u) << r;
+    z[r] = fmaxf(a, b);
+    z[r + 8] = fminf(a, b);
+  }
+}
+
+// Backward of dropout_groupsort_pairs, in place: g holds d/d(sorted output) and becomes
+// d/d(pre-dropout value): the routing of act_backward_tile<GROUPSORT>, then times keep * scale.
+__device__ __forceinline__ void dropout_groupsort_pairs_backward(f32x16& g, uint32_t gt, uint32_t eq, uint32_t ka,
+                                                                 uint32_t kb, int half, float scale) {
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const float gmx = g[r], gmn = g[r + 8];
+    const bool first_max = (gt >> r) & 1u, tie = (eq >> r) & 1u;
+    const bool ba = (ka >> acc_row(r, half)) & 1u, bb = (kb >> acc_row(r, half)) & 1u;
+    const float halfsum = gmx / 2.0f + gmn / 2.0f;
+    const float ga = tie ? halfsum : (first_max ? gmx : gmn);
+    const float gb = tie ? halfsum : (first_max ? gmn : gmx);
+    g[r] = ba ? ga * scale : 0.f;
+    g[r + 8] = bb ? gb * scale : 0.f;
+  }
 }
 
 // Backward of the activation on the four accumulator blocks of a wave tile, in place: g holds
@@ -131,7 +204,8 @@ __device__ __forceinline__ void gather_ft(const f32x16& z3, int half, float (&ft
 }
 
 // Layers 1-2 of the MLP of one wave tile: z1/z2 become the post-dropout-ReLU activations a1^T,
-// a2^T.  q1: hoisted layer-1 A operands.  A: the activation (GROUPSORT: eval mode only).
+// a2^T.  q1: hoisted layer-1 A operands.  A: the activation (GROUPSORT with DROP: the sort of the
+// dropped values, dropout_groupsort_tile).
 template <bool DROP = true, Act A = RELU>
 __device__ __forceinline__ void mlp12_tile(const float* Q2s, const float (&q1)[4][5], const float* u_row,
                                            const float* b2, const float (&h)[C], const uint32_t (&kw1)[4],
@@ -146,9 +220,9 @@ __device__ __forceinline__ void mlp12_tile(const float* Q2s, const float (&q1)[4
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) z1[mb] = mfma32(q1[mb][s], bs, z1[mb]);
   }
-  static_assert(A == RELU || !DROP, "GroupSort dynamics run in eval mode only (no dropout)");
   if constexpr (A == GROUPSORT) {
-    groupsort_tile(z1);
+    if constexpr (DROP) dropout_groupsort_tile(z1, kw1, half, scale);
+    else groupsort_tile(z1);
   } else {
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) dropout_relu<DROP>(z1[mb], kw1[mb], half, scale);
@@ -169,7 +243,8 @@ __device__ __forceinline__ void mlp12_tile(const float* Q2s, const float (&q1)[4
     __builtin_amdgcn_sched_barrier(0);   // bound the LDS-read hoisting window to one k-block
   }
   if constexpr (A == GROUPSORT) {
-    groupsort_tile(z2);
+    if constexpr (DROP) dropout_groupsort_tile(z2, kw2, half, scale);
+    else groupsort_tile(z2);
   } else {
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) dropout_relu<DROP>(z2[mb], kw2[mb], half, scale);

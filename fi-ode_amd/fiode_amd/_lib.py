@@ -154,6 +154,9 @@ def _load():
         "fiode_lyap_workspace_bytes": (ct.c_size_t, [ct.POINTER(LyapConfig), ct.POINTER(DynConfig)]),
         "fiode_lyap_step": (ct.c_int, [_vp, ct.POINTER(LyapConfig), ct.POINTER(DynConfig), ct.POINTER(DynWeights),
                                        ct.POINTER(LyapIO), ct.POINTER(LyapGrads), _vp, ct.c_size_t]),
+        "fiode_lyap_step_act": (ct.c_int, [_vp, ct.POINTER(LyapConfig), ct.POINTER(DynConfig),
+                                           ct.POINTER(DynWeights), ct.POINTER(LyapIO), ct.POINTER(LyapGrads), _vp,
+                                           ct.c_size_t, ct.c_int32]),
         "fiode_qp_forward": (ct.c_int, [_vp, ct.c_int32, ct.c_int32, _vp, _vp, ct.c_int32, ct.c_float, _vp, _vp,
                                         _vp, _vp, ct.c_size_t]),
         "fiode_qp_backward": (ct.c_int, [_vp, ct.c_int32, ct.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

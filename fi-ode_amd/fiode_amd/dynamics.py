@@ -10,8 +10,10 @@ through ``_EvalDotFn``, whose backward is the fused HIP vector-Jacobian product
 (``ops.dyn_eval_backward``) for both activations, and the gradients reach the parameters through
 ``effective_weights()``' own autograd (the Cayley maps).  One derivative only: a double backward
 raises.  The training-mode eval_dot with dropout is fused, with its backward, into the Lyapunov
-step and the train_ode solve (``fiode_amd.lyapunov``), which implement 'ReLU' only: training a
-GroupSort module raises NotImplementedError.
+step and the train_ode solve (``fiode_amd.lyapunov``).  The Lyapunov step implements both
+activations, GroupSort behind the opt-in switch ``ops.GROUPSORT_TRAINING``; the train_ode solves
+implement 'ReLU' only.  Training a GroupSort module raises NotImplementedError with the switch off,
+and with it on once the train_ode branch is active.
 """
 from __future__ import annotations
 
@@ -78,8 +80,9 @@ class OrthoClassDynProjectSimplexLips(nn.Module):
             self.activation = nn.ReLU()
         elif activation == "GroupSort":
             # classification.py:44-48 (the reference's config default): no parameters or buffers, so
-            # the state_dict keys are the ReLU module's.  Evaluation, ODE solves and certification
-            # only: the training kernels refuse it (ops.require_relu)
+            # the state_dict keys are the ReLU module's.  Evaluation, ODE solves, certification and,
+            # with ops.GROUPSORT_TRAINING on, the Lyapunov training step; the train_ode solves
+            # refuse it (ops.require_relu)
             self.activation = GroupSort()
         else:
             raise NotImplementedError(f"activation {activation!r}: the fused dynamics kernels implement 'ReLU' "

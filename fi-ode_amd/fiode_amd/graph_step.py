@@ -74,7 +74,7 @@ class GraphTrainStep:
         dev = x.device
         if dev.type != "cuda":
             raise ValueError("GraphTrainStep needs ROCm device tensors")
-        module.require_trainable_dynamics("GraphTrainStep")     # before the warm-up or a capture
+        module.require_trainable_dynamics("GraphTrainStep", step=True)     # before the warm-up or a capture
         self.module, self.opt, self.reducer, self.world, self.act = module, optimizer, reducer, world, act
         self.check_every, self.n_replays = int(check_every), 0
         self.piped, self.early = [], False
@@ -290,6 +290,9 @@ class GraphTrainStep:
         if not distinct(self.module.streams.all()):
             raise RuntimeError("GraphTrainStep: two roles of the captured step share one HIP stream "
                                "(use fiode_amd.streams.new_stream for side streams, not the torch pool)")
+        # (again at every capture: a recapture after the train_ode branch became active would put the
+        # ReLU-only solve into the graph of a GroupSort module)
+        self.module.require_trainable_dynamics("GraphTrainStep", step=True)
         self.one_graph = self.single or self.comm == "graph"
         # zeroed split-K counter words for the GEMMs of streams this capture makes (ops._Workspace:
         # taken from an arena zeroed here, not filled by the replay on the step's chain)

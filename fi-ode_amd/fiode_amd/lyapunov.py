@@ -617,7 +617,7 @@ class LyapunovLearning(nn.Module):
 
     def compute_loss(self, x, y, batch_size=None, act="relu", h=None, masks=None, debug=False):
         """pl_modules.py:390-502 with the per-sample graph fused (LyapunovLossFn)."""
-        self.require_trainable_dynamics("LyapunovLearning.compute_loss")
+        self.require_trainable_dynamics("LyapunovLearning.compute_loss", step=True)
         step_stream = torch.cuda.current_stream(x.device) if x.is_cuda else None
         with self.streams.scope(step_stream):
             return self._compute_loss(x, y, h=h, masks=masks, debug=debug)
@@ -683,11 +683,18 @@ class LyapunovLearning(nn.Module):
                     3: "dt underflow"}.get(status, "a cross-workgroup exchange timed out")
             raise RuntimeError(f"train_ode solve failed (status {status}: {what}); the step's loss is NaN")
 
-    def require_trainable_dynamics(self, what: str) -> None:
-        """The training kernels (the fused Lyapunov step, the train_ode solves) apply ReLU: a module
-        whose dynamics use another activation (GroupSort: evaluation, ODE solves and certification
-        only) must not reach them -- NotImplementedError, before any tensor is touched."""
-        ops.require_relu(self.dyn_fun.dyn_cfg(), what)
+    def ode_branch_active(self) -> bool:
+        """Whether a training step now runs the train_ode solve beside the Lyapunov step
+        (pl_modules.py:490)."""
+        return bool(self.train_ode and self.current_epoch > self.train_ode_epoch)
+
+    def require_trainable_dynamics(self, what: str, step: bool = False) -> None:
+        """The train_ode solves apply ReLU, and so does the fused Lyapunov step unless
+        ``ops.GROUPSORT_TRAINING`` is on: a module whose dynamics use another activation must not
+        reach a kernel that does not implement it -- NotImplementedError, before any tensor is
+        touched.  ``step``: the caller runs a training step (the Lyapunov step, and the solve only
+        when the train_ode branch is active); else it is about the solve itself."""
+        ops.require_relu(self.dyn_fun.dyn_cfg(), what, lyap_only=step and not self.ode_branch_active())
 
     def ode_plan(self, batch: int, masks: Optional[torch.Tensor] = None) -> dict:
         """Solver plan of the train_ode solve (make_solver_params(train_ode_solver, train_ode_tol),

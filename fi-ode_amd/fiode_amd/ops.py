@@ -6,6 +6,7 @@ never reach a kernel), runs on the caller's current HIP stream, and caches works
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as ct
 from dataclasses import dataclass
 from typing import Dict, Optional
@@ -55,10 +56,35 @@ TRAIN_RELU_ONLY = ("{what}: GroupSort dynamics are supported for evaluation, ODE
                    "activation='ReLU' only")
 
 
-def require_relu(dyn: DynCfg, what: str) -> None:
-    """The training kernels apply ReLU: refuse any other activation before anything is launched."""
-    if dyn.activation != "ReLU":
-        raise NotImplementedError(TRAIN_RELU_ONLY.format(what=what))
+# Opt-in switch of GroupSort TRAINING through the fused Lyapunov step (fiode_lyap_step_act with
+# FIODE_ACT_GROUPSORT: a = GroupSort(dropout(z)), forward and backward).  Off: every training path
+# refuses a GroupSort DynCfg as before.  On: ``lyap_step`` (and with it LyapunovLearning.compute_loss
+# and GraphTrainStep while the train_ode branch is not active) takes it; the train_ode solves
+# (``odetrain_*``, LyapunovLearning.ode_plan) keep refusing -- their kernels are ReLU-only.
+GROUPSORT_TRAINING = False
+
+
+@contextlib.contextmanager
+def groupsort_training(on: bool = True):
+    """Inside: ``GROUPSORT_TRAINING = on``; the earlier value is back on exit, after an exception too."""
+    global GROUPSORT_TRAINING
+    before = GROUPSORT_TRAINING
+    GROUPSORT_TRAINING = bool(on)
+    try:
+        yield
+    finally:
+        GROUPSORT_TRAINING = before
+
+
+def require_relu(dyn: DynCfg, what: str, lyap_only: bool = False) -> None:
+    """The one gate of the training kernels: refuse an activation they do not implement before
+    anything is launched.  ReLU passes everywhere.  GroupSort passes only with ``lyap_only`` (the
+    caller launches the fused Lyapunov step and no train_ode solve) while GROUPSORT_TRAINING is on."""
+    if dyn.activation == "ReLU":
+        return
+    if lyap_only and GROUPSORT_TRAINING and dyn.activation == "GroupSort":
+        return
+    raise NotImplementedError(TRAIN_RELU_ONLY.format(what=what))
 
 
 def _stream(dev: torch.device) -> ct.c_void_p:
@@ -152,7 +178,8 @@ def lyap_step(x_feat: torch.Tensor, y: torch.Tensor, weights: Dict[str, torch.Te
               h: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None, debug: bool = False,
               out: Optional[dict] = None, events=None, offset_dev: Optional[torch.Tensor] = None,
               exp_draws: Optional[torch.Tensor] = None, kappa_dev: Optional[torch.Tensor] = None):
-    """The fused training step (fiode_lyap_step).  Returns (scalars[8], grads dict, debug dict).
+    """The fused training step (fiode_lyap_step_act).  Returns (scalars[8], grads dict, debug dict).
+    ``dyn.activation``: 'ReLU', or 'GroupSort' while ``GROUPSORT_TRAINING`` is on (require_relu).
     ``events``: optional list of len(_lib.LYAP_KERNELS)+1 torch.cuda.Event(enable_timing=True),
     recorded by the library around each of its kernels on the current stream.
     ``offset_dev``: optional int64 [1] device tensor added to ``offset`` by the kernels (a captured
@@ -161,7 +188,8 @@ def lyap_step(x_feat: torch.Tensor, y: torch.Tensor, weights: Dict[str, torch.Te
     of them, the reference's draw shapes) instead of the in-kernel Philox draws.
     ``debug``: also returns the per-row outputs, the Exp(1) variates the sampler used
     (``exp_draws``) and the dropout keep words (``keep_words`` int32 [4, N, 4])."""
-    require_relu(dyn, "lyap_step")
+    require_relu(dyn, "lyap_step", lyap_only=True)
+    act = _act(dyn)
     dev = x_feat.device
     B = x_feat.shape[0]
     S = int(sample_size)
@@ -235,9 +263,14 @@ def lyap_step(x_feat: torch.Tensor, y: torch.Tensor, weights: Dict[str, torch.Te
     lib = L.lib()
     nbytes = lib.fiode_lyap_workspace_bytes(ct.byref(cfg), ct.byref(dc))
     ws = _Workspace.get(dev, nbytes, "lyap")
-    rc = lib.fiode_lyap_step(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), ct.byref(io), ct.byref(cg),
-                             ct.c_void_p(ws.data_ptr()), ct.c_size_t(ws.numel()))
-    L.check(rc, "fiode_lyap_step")
+    if act == L.FIODE_ACT_RELU and not hasattr(lib, "fiode_lyap_step_act"):
+        # an older build under an A/B (FIODE_LIB, _lib._load): its fiode_lyap_step is the ReLU case
+        rc = lib.fiode_lyap_step(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), ct.byref(io),
+                                 ct.byref(cg), ct.c_void_p(ws.data_ptr()), ct.c_size_t(ws.numel()))
+    else:
+        rc = lib.fiode_lyap_step_act(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), ct.byref(io),
+                                     ct.byref(cg), ct.c_void_p(ws.data_ptr()), ct.c_size_t(ws.numel()), act)
+    L.check(rc, "fiode_lyap_step_act")
     del ws_w
     return scalars, grads, dbg
 

@@ -172,13 +172,27 @@ FIODE_API int fiode_dyn_eval(void* stream, const fiode_dyn_config* dyn, const fi
  * check (the activation included) runs before the workspace-size check, and nothing is launched
  * on an error.  FIODE_ABI_VERSION does not move for them: they are new symbols only, and the
  * structs, the existing prototypes and their behaviour are unchanged, so a caller built against
- * ABI 5 before they existed still binds and runs as before.  The training entry points
- * (fiode_lyap_step, fiode_odetrain_*) implement ReLU only. */
+ * ABI 5 before they existed still binds and runs as before.  Of the training entry points,
+ * the fused Lyapunov step has both activations (fiode_lyap_step_act below); the train_ode solves
+ * (fiode_odetrain_*) implement ReLU only. */
 enum { FIODE_ACT_RELU = 0, FIODE_ACT_GROUPSORT = 1 };
 FIODE_API int fiode_dyn_eval_act(void* stream, const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
                                  int32_t batch, int32_t rows_per_image, const float* x_feat, const float* h,
                                  float* f, int32_t* exit_iter, void* workspace, size_t workspace_bytes,
                                  int32_t activation);
+
+/* fiode_lyap_step with the activation of the dynamics MLP (same rules as the other *_act entry
+ * points: fiode_lyap_step is the FIODE_ACT_RELU case, the workspace is fiode_lyap_workspace_bytes,
+ * another activation is FIODE_EINVAL, every argument check comes before the workspace-size check,
+ * nothing is launched on an error; a new symbol only, FIODE_ABI_VERSION does not move).
+ * FIODE_ACT_GROUPSORT trains a = GroupSort(dropout(z)) per hidden layer (classification.py:98, 100):
+ * with the unit's keep bit k, d = k ? z / (1 - p) : 0, then a[u] = max(d[u], d[u + M/2]) and
+ * a[u + M/2] = min(d[u], d[u + M/2]); both passes (loss and logging) use it.  Backward: the max / min
+ * gradients go back to the pair's members by the order of d, a tie (two dropped members are one)
+ * gives both g_max / 2 + g_min / 2, and the result is multiplied by k / (1 - p). */
+FIODE_API int fiode_lyap_step_act(void* stream, const fiode_lyap_config* cfg, const fiode_dyn_config* dyn,
+                                  const fiode_dyn_weights* w, const fiode_lyap_io* io, fiode_lyap_grads* grads,
+                                  void* workspace, size_t workspace_bytes, int32_t activation);
 
 /* The vector-Jacobian product of fiode_dyn_eval_act (the reference's eval_dot is an ordinary
  * differentiable torch function, classification.py:104-126): given g_f [N][C] = d L / d f it writes
@@ -190,8 +204,8 @@ FIODE_API int fiode_dyn_eval_act(void* stream, const fiode_dyn_config* dyn, cons
  * (barrier_projection.py:271-311); a GroupSort tie splits the gradient in half (torch.maximum /
  * minimum).  dbg (nullable): optional per-row outputs, NULL members are not written.  Argument
  * checks, error codes and batch == 0 as fiode_dyn_eval_act.  With this, the eval-mode dynamics are
- * differentiable outside the training entry points (fiode_lyap_step, fiode_odetrain_*), which keep
- * their own fused backward with dropout and implement ReLU only. */
+ * differentiable outside the training entry points (fiode_lyap_step[_act], fiode_odetrain_*), which
+ * keep their own fused backward with dropout (fiode_odetrain_*: ReLU only). */
 typedef struct fiode_dyn_eval_debug {
   float* f;              /* [N][C] the recomputed eval_dot (bit-equal to the forward's)           */
   float* qp_lower;       /* [N][C] QP lower bound                                                 */
