@@ -18,6 +18,9 @@
 //   gradients (Q3^T, Q2^T via LDS images, Q1^T via a zero-padded LDS image), writing the per-
 //   (row, eval) activation gradients gft / gz2 / gz1.
 // Weight gradients: the training step's wgrad chain over rows r = b*E + e (wgrad.h).
+// Activation: ReLU, or GroupSort on the 16-row kernels (k_ot_fwd<GROUPSORT> / k_ot_bwd<SN, GROUPSORT>,
+// rk4 only, for every B): wave p holds hidden blocks (p, p + 4), so a sort pair (u, u + 64) is one
+// lane's registers in both directions; the forward saves each pair's order and tie for the backward.
 #include <type_traits>
 #include "common.h"
 #include "tile.h"
@@ -90,7 +93,13 @@ struct OTArgs {
   // dopri5 (method FIODE_ODE_DOPRI5): E = 2 + 6 A is the eval capacity, the solve's own count is in imeta
   int method, A;
   double rtol, atol, t0d, t1d;
-  float* ys;                   // [A][B][C] the state y_n attempt n starts from
+  union {                      // (one kernel argument slot: the two solves never meet)
+    float* ys;                 // dopri5: [A][B][C] the state y_n attempt n starts from
+    // GroupSort (rk4, 16-row tiles): the pair codes the forward saves for the backward, appended to
+    // the workspace behind the ReLU layout.  [B][E][16]: entry 4 hb + q = the codes of pairs
+    // 16 hb + 4q .. + 3, layer 1 in the low byte and layer 2 in the high one (mlp16_part)
+    uint16_t* codes;
+  };
   double* alog;                // [A][ALOG_W] per attempt (ALOG_*)
   double* meta;                // [META_N] initial-step scalars (META_*)
   int32_t* imeta;              // [8]: nfe, attempts, status (read by the backward and the weight chain)
@@ -149,6 +158,9 @@ struct OtShared {
 #endif
 
 // one eval for this workgroup's tile: stage input h (per lane, its row) -> k (per lane)
+// A = GROUPSORT: layer 1 replicated on every wave (no layer-1 barrier), kw2p = gs_keep16 of the
+// eval's layer-2 keep words, and the pair codes saved beside a1 / a2.
+template <Act A = RELU>
 __device__ void ot_eval(const OTArgs& a, const T16W& w, OtShared& sh, int e, int p, int b, bool valid, int lane, int q,
                         int j, const f32x4v (&uacc)[8], const uint32_t (&kw1)[4], uint32_t kw2p, const float (&h)[C],
                         float (&k)[C]) {
@@ -168,10 +180,15 @@ __device__ void ot_eval(const OTArgs& a, const T16W& w, OtShared& sh, int e, int
     lower[i] = -a.d.alpha_1 * (expf(a.d.sigma_1 * h[i]) - 1.0f);
     asm volatile("" ::"v"(lower[i]));          // keep it here (IR passes would sink it to its use)
   }
-  mlp16_part<OT_SHARE_L1 != 0>(w, uacc, h, kw1, kw2p, a.drop_scale, p, q, valid ? a.a1 + r * M : nullptr,
-                               valid ? a.a2 + r * M : nullptr, &sh.zpart[p][lane][0], sh.z1x);
+  if constexpr (A == GROUPSORT)
+    mlp16_part<false, GROUPSORT, true>(w, uacc, h, kw1, kw2p, a.drop_scale, p, q, valid ? a.a1 + r * M : nullptr,
+                                       valid ? a.a2 + r * M : nullptr, &sh.zpart[p][lane][0], nullptr,
+                                       valid ? a.codes + r * 16 : nullptr);
+  else
+    mlp16_part<OT_SHARE_L1 != 0>(w, uacc, h, kw1, kw2p, a.drop_scale, p, q, valid ? a.a1 + r * M : nullptr,
+                                 valid ? a.a2 + r * M : nullptr, &sh.zpart[p][lane][0], sh.z1x);
 #pragma unroll
-  for (int i = 0; i < (OT_SHARE_L1 ? 78 : 96); ++i) {
+  for (int i = 0; i < (A == RELU && OT_SHARE_L1 ? 78 : 96); ++i) {
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // one MFMA
     __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);     // then up to three VALU
   }
@@ -245,6 +262,7 @@ __global__ __launch_bounds__(256) void k_ot_masks(OTArgs a) {
   }
 }
 
+template <Act A = RELU>
 __global__ __launch_bounds__(256) void k_ot_fwd(OTArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   OtShared& sh = *reinterpret_cast<OtShared*>(smem);
@@ -258,7 +276,7 @@ __global__ __launch_bounds__(256) void k_ot_fwd(OTArgs a) {
   const bool valid = b < a.B;
   const int bb = valid ? b : a.B - 1;
   T16W w;                     // this wave's weight operands, in registers for the whole solve
-  load_t16w(a.Q1, a.Q2, M, a.Q3, M, a.b2, a.b3, p, q, j, w);
+  load_t16w<A>(a.Q1, a.Q2, M, a.Q3, M, a.b2, a.b3, p, q, j, w);
   // u[b] = U_x x_b + bx + b1 for this tile's rows
   for (int t = threadIdx.x; t < TR * M; t += blockDim.x) {
     const int rb = blockIdx.x * TR + t / M, i = t % M;
@@ -287,7 +305,10 @@ __global__ __launch_bounds__(256) void k_ot_fwd(OTArgs a) {
     }
     const uint4 q1 = kwp[((size_t)e * 2 + 0) * a.B + bb];
     w1[0] = q1.x; w1[1] = q1.y; w1[2] = q1.z; w1[3] = q1.w;
-    w2 = reinterpret_cast<const uint32_t*>(kwp + ((size_t)e * 2 + 1) * a.B + bb)[p];   // layer-2 word of part p
+    if constexpr (A == GROUPSORT)       // layer-2 keep bits of blocks p, p + 4
+      w2 = gs_keep16(reinterpret_cast<const uint32_t*>(kwp + ((size_t)e * 2 + 1) * a.B + bb), p);
+    else
+      w2 = reinterpret_cast<const uint32_t*>(kwp + ((size_t)e * 2 + 1) * a.B + bb)[p];   // layer-2 word of part p
   };
   uint32_t kc1[4], kc2, kn1[4], kn2;
   fetch(0, kc1, kc2);
@@ -302,7 +323,7 @@ __global__ __launch_bounds__(256) void k_ot_fwd(OTArgs a) {
 #define OT_STAGE(E_, H_, K_)                                                             \
     {                                                                                    \
       if ((E_) + 1 < eN) fetch((E_) + 1, kn1, kn2);                                      \
-      ot_eval(a, w, sh, (E_), p, b, valid, lane, q, j, uacc, kc1, kc2, H_, K_);     \
+      ot_eval<A>(a, w, sh, (E_), p, b, valid, lane, q, j, uacc, kc1, kc2, H_, K_);  \
       _Pragma("unroll") for (int t = 0; t < 4; ++t) kc1[t] = kn1[t];                   \
       kc2 = kn2;                                                                         \
     }
@@ -536,6 +557,51 @@ __device__ __forceinline__ void load_vjp_in(const OTArgs& a, int p, int e, int b
   for (int o = 0; o < 2; ++o) in.a1[o] = *reinterpret_cast<const f32x4*>(a.a1 + r * M + 16 * (2 * p + o) + 4 * q);
 }
 
+// GroupSort: the backward routes by the saved pair codes and masks by the keep bits, where ReLU
+// masks by the saved a1 / a2.  code: the codes of this lane's pairs 16p + 4q .. + 3 (layer 1 in
+// bits 0..7, layer 2 in bits 8..15); k1 / k2: gs_keep16 of the eval's layer-1 / layer-2 keep words.
+struct VjpInGs {
+  float h[C], ft[C], v[C], mu;
+  uint32_t code, k1, k2;
+};
+template <Act A>
+using VjpInOf = std::conditional_t<A == GROUPSORT, VjpInGs, VjpIn>;
+
+__device__ __forceinline__ void load_vjp_in(const OTArgs& a, int p, int e, int b, bool valid, int q, VjpInGs& in) {
+  const int bb = valid ? b : a.B - 1;
+  const int ee = e < 0 ? 0 : e;
+  const size_t r = (size_t)bb * a.E + ee;
+  load_row10(a.hs + r * C, in.h);
+  load_row10(a.ftw + r * C, in.ft);
+  load_row10(a.vw + r * C, in.v);
+  in.mu = a.muw[r];
+  in.code = a.codes[r * 16 + 4 * p + q];
+  if (a.dropout_mode == FIODE_DROPOUT_OFF) {
+    in.k1 = in.k2 = 0xFFFFFFFFu;
+  } else {
+    const uint32_t* kw = a.kw + ((size_t)ee * 2 * a.B + bb) * 4;
+    in.k1 = gs_keep16(kw, p);
+    in.k2 = gs_keep16(kw + (size_t)a.B * 4, p);
+  }
+}
+
+// GroupSort's gradient routing for this lane's 4 pairs: gx / gy arrive as the gradients of the max /
+// min outputs and leave as those of the pair's members (u, u + 64).  The member that held the larger
+// dropped value takes g_max, the other g_min, a tie gives both g_max / 2 + g_min / 2; then g_z = g_d *
+// keep * scale.  code: bits 0..3 order, 4..7 tie (pair_code4); kx / ky: keep bits 0..3.
+__device__ __forceinline__ void route4(f32x4v& gx, f32x4v& gy, uint32_t code, uint32_t kx, uint32_t ky, float scale) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const float gmx = gx[t], gmn = gy[t];
+    const float half = gmx * 0.5f + gmn * 0.5f;
+    const bool first = (code >> t) & 1u, tie = (code >> (4 + t)) & 1u;
+    const float ga = tie ? half : (first ? gmx : gmn);
+    const float gb = tie ? half : (first ? gmn : gmx);
+    gx[t] = ((kx >> t) & 1u) ? ga * scale : 0.f;
+    gy[t] = ((ky >> t) & 1u) ? gb * scale : 0.f;
+  }
+}
+
 // The backward's weight operands of one wave (part p), in registers for the whole kernel: q2t[o][hb]
 // = Q2^T[16 (2p + o) + j][16 hb + 4q ..] = Q2[16 hb + 4q + t][16 (2p + o) + j]; q1t[o] =
 // Q1^T[j][16 (2p + o) + 4q ..] (0 for j >= C).
@@ -571,28 +637,48 @@ __device__ __forceinline__ void vjp_row_math(const OTArgs& a, const In& in, VjpR
 
 // g_z2 blocks 2P, 2P+1 of one VJP: Q3^T g_ft, masked by the saved a2 and the dropout scale;
 // stored to gz2 (nullable row) and to the LDS exchange.
-template <int P>
+// A = GROUPSORT: blocks P, P + 4 -- g_a2 of the max / min outputs of the lane's pairs, routed to the
+// pair's members (route4) in registers.
+template <int P, Act A = RELU>
 __device__ __forceinline__ void gz2_pair(const OTArgs& a, const float (&q3t)[8][3], const float (&gft)[C],
-                                         const VjpIn& in, int q, int lane, float* gz2row, float (*gax)[64][4]) {
+                                         const VjpInOf<A>& in, int q, int lane, float* gz2row, float (*gax)[64][4]) {
+  if constexpr (A == GROUPSORT) {
+    f32x4v g[2] = {z4(), z4()};
 #pragma unroll
-  for (int o = 0; o < 2; ++o) {
-    constexpr int hb0 = 2 * P;
-    f32x4v g = z4();
+    for (int o = 0; o < 2; ++o)
 #pragma unroll
-    for (int s = 0; s < 3; ++s) g = mfma16(q3t[hb0 + o][s], sel4(gft, s, q), g);
-    const f32x4 act = in.a2[o];
+      for (int s = 0; s < 3; ++s) g[o] = mfma16(q3t[P + 4 * o][s], sel4(gft, s, q), g[o]);
+    route4(g[0], g[1], in.code >> 8, in.k2 >> (4 * q), in.k2 >> (16 + 4 * q), a.drop_scale);
 #pragma unroll
-    for (int t = 0; t < 4; ++t) g[t] = act[t] > 0.f ? g[t] * a.drop_scale : 0.f;
-    if (gz2row) *reinterpret_cast<f32x4*>(gz2row + 16 * (hb0 + o) + 4 * q) = f32x4{g[0], g[1], g[2], g[3]};
-    *reinterpret_cast<f32x4*>(&gax[hb0 + o][lane][0]) = f32x4{g[0], g[1], g[2], g[3]};
+    for (int o = 0; o < 2; ++o) {
+      const f32x4 v = f32x4{g[o][0], g[o][1], g[o][2], g[o][3]};
+      if (gz2row) *reinterpret_cast<f32x4*>(gz2row + 16 * (P + 4 * o) + 4 * q) = v;
+      *reinterpret_cast<f32x4*>(&gax[P + 4 * o][lane][0]) = v;
+    }
+  } else {
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      constexpr int hb0 = 2 * P;
+      f32x4v g = z4();
+#pragma unroll
+      for (int s = 0; s < 3; ++s) g = mfma16(q3t[hb0 + o][s], sel4(gft, s, q), g);
+      const f32x4 act = in.a2[o];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) g[t] = act[t] > 0.f ? g[t] * a.drop_scale : 0.f;
+      if (gz2row) *reinterpret_cast<f32x4*>(gz2row + 16 * (hb0 + o) + 4 * q) = f32x4{g[0], g[1], g[2], g[3]};
+      *reinterpret_cast<f32x4*>(&gax[hb0 + o][lane][0]) = f32x4{g[0], g[1], g[2], g[3]};
+    }
   }
 }
 
-template <bool SN>
+// A = GROUPSORT: wave p owns hidden blocks (p, p + 4) in all three products (wv from k_ot_bwd<SN,
+// GROUPSORT>), so both members of every sort pair are one lane's registers and the routing (route4)
+// needs no exchange and no barrier of its own.
+template <bool SN, Act A = RELU>
 __device__ void ot_vjp(const OTArgs& a, const VjpW& wv, const float (&q3t)[8][3],
                        OtBwdShared& sh, int buf, int p, int e, int b, bool valid, int lane, int q, int j,
-                       const VjpIn& in, const VjpRow& rw, const VjpIn& nin, VjpRow& nrw, const float (&g)[C],
-                       float (&gy_out)[C]) {
+                       const VjpInOf<A>& in, const VjpRow& rw, const VjpInOf<A>& nin, VjpRow& nrw,
+                       const float (&g)[C], float (&gy_out)[C]) {
   const int bb = valid ? b : a.B - 1;
   const size_t r = (size_t)bb * a.E + e;
 #ifdef OT_PROFILE
@@ -628,10 +714,10 @@ __device__ void ot_vjp(const OTArgs& a, const VjpW& wv, const float (&q3t)[8][3]
   // wave computing all 8)
   {
     switch (p) {              // wave-uniform: static register indices in each case
-      case 0: gz2_pair<0>(a, q3t, gft, in, q, lane, valid ? a.gz2 + r * M : nullptr, sh.gax); break;
-      case 1: gz2_pair<1>(a, q3t, gft, in, q, lane, valid ? a.gz2 + r * M : nullptr, sh.gax); break;
-      case 2: gz2_pair<2>(a, q3t, gft, in, q, lane, valid ? a.gz2 + r * M : nullptr, sh.gax); break;
-      default: gz2_pair<3>(a, q3t, gft, in, q, lane, valid ? a.gz2 + r * M : nullptr, sh.gax); break;
+      case 0: gz2_pair<0, A>(a, q3t, gft, in, q, lane, valid ? a.gz2 + r * M : nullptr, sh.gax); break;
+      case 1: gz2_pair<1, A>(a, q3t, gft, in, q, lane, valid ? a.gz2 + r * M : nullptr, sh.gax); break;
+      case 2: gz2_pair<2, A>(a, q3t, gft, in, q, lane, valid ? a.gz2 + r * M : nullptr, sh.gax); break;
+      default: gz2_pair<3, A>(a, q3t, gft, in, q, lane, valid ? a.gz2 + r * M : nullptr, sh.gax); break;
     }
   }
   __syncthreads();
@@ -661,13 +747,21 @@ __device__ void ot_vjp(const OTArgs& a, const VjpW& wv, const float (&q3t)[8][3]
     __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);     // then up to six VALU
   }
   __builtin_amdgcn_sched_barrier(0);
+  if constexpr (A == GROUPSORT) {
+    route4(gb[0], gb[1], in.code, in.k1 >> (4 * q), in.k1 >> (16 + 4 * q), a.drop_scale);
 #pragma unroll
-  for (int o = 0; o < 2; ++o) {
-    const f32x4 act = in.a1[o];
+    for (int o = 0; o < 2; ++o)
+      if (valid)
+        *reinterpret_cast<f32x4*>(a.gz1 + r * M + 16 * (p + 4 * o) + 4 * q) = f32x4{gb[o][0], gb[o][1], gb[o][2], gb[o][3]};
+  } else {
 #pragma unroll
-    for (int t = 0; t < 4; ++t) gb[o][t] = act[t] > 0.f ? gb[o][t] * a.drop_scale : 0.f;
-    if (valid)
-      *reinterpret_cast<f32x4*>(a.gz1 + r * M + 16 * (2 * p + o) + 4 * q) = f32x4{gb[o][0], gb[o][1], gb[o][2], gb[o][3]};
+    for (int o = 0; o < 2; ++o) {
+      const f32x4 act = in.a1[o];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) gb[o][t] = act[t] > 0.f ? gb[o][t] * a.drop_scale : 0.f;
+      if (valid)
+        *reinterpret_cast<f32x4*>(a.gz1 + r * M + 16 * (2 * p + o) + 4 * q) = f32x4{gb[o][0], gb[o][1], gb[o][2], gb[o][3]};
+    }
   }
   OT_MARK(12);
   // partial g_h^T over hidden blocks 2p, 2p+1 (Q1^T image, rows >= 10 zero)
@@ -691,7 +785,7 @@ __device__ void ot_vjp(const OTArgs& a, const VjpW& wv, const float (&q3t)[8][3]
   OT_MARK(15);
 }
 
-template <bool SN>
+template <bool SN, Act A = RELU>
 __global__ __launch_bounds__(256) void k_ot_bwd(OTArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   OtBwdShared& sh = *reinterpret_cast<OtBwdShared*>(smem);
@@ -700,6 +794,15 @@ __global__ __launch_bounds__(256) void k_ot_bwd(OTArgs a) {
   VjpW wv;
 #pragma unroll
   for (int o = 0; o < 2; ++o) {
+    if constexpr (A == GROUPSORT) {       // this wave's hidden blocks: p, p + 4
+#pragma unroll
+      for (int hb = 0; hb < 8; ++hb)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) wv.q2t[o][hb][t] = a.Q2[(16 * hb + 4 * q + t) * M + 16 * (p + 4 * o) + j];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) wv.q1t[o][t] = j < C ? a.Q1[(16 * (p + 4 * o) + 4 * q + t) * C + j] : 0.f;
+      continue;
+    }
 #pragma unroll
     for (int hb = 0; hb < 8; ++hb)
 #pragma unroll
@@ -721,7 +824,7 @@ __global__ __launch_bounds__(256) void k_ot_bwd(OTArgs a) {
     for (int i = 0; i < C; ++i) gy[i] = 0.f;
   const float third = 1.0f / 3.0f;
   int buf = 0;
-  VjpIn cur, nxt;
+  VjpInOf<A> cur, nxt;
   VjpRow crw, nrw;
   load_vjp_in(a, p, a.E - 1, b, valid, q, cur);
   vjp_row_math<SN>(a, cur, crw);
@@ -729,7 +832,7 @@ __global__ __launch_bounds__(256) void k_ot_bwd(OTArgs a) {
   // computes its row math between its own MFMA chains
 #define OT_VJP(E_, G_)                                                                  \
   load_vjp_in(a, p, (E_) - 1, b, valid, q, nxt);                                        \
-  ot_vjp<SN>(a, wv, q3t, sh, buf, p, (E_), b, valid, lane, q, j, cur, crw, nxt, nrw, G_, gY); \
+  ot_vjp<SN, A>(a, wv, q3t, sh, buf, p, (E_), b, valid, lane, q, j, cur, crw, nxt, nrw, G_, gY); \
   cur = nxt;                                                                            \
   crw = nrw;                                                                            \
   buf ^= 1;
@@ -1966,8 +2069,24 @@ OtLayout ot_layout(int B, int E, int A = 0) {
   return L;
 }
 
+// GroupSort: the pair codes of the forward, 32 bytes per (row, eval), appended behind the ReLU layout
+// (which does not move): the region starts at ot_layout().total.
+size_t gs_code_bytes(int B, int E) { return al((size_t)B * E * 32); }
+
+// The activation's own checks, ahead of every other one: an activation outside the enum is
+// FIODE_EINVAL, GroupSort with the dopri5 solve (not implemented) FIODE_ESHAPE.
+int check_act(const fiode_odetrain_config* cfg, int32_t activation) {
+  if (activation != FIODE_ACT_RELU && activation != FIODE_ACT_GROUPSORT) return FIODE_EINVAL;
+  if (activation == FIODE_ACT_GROUPSORT && cfg && cfg->method == FIODE_ODE_DOPRI5) return FIODE_ESHAPE;
+  return FIODE_OK;
+}
+
+// need (nullable): the workspace-size check is left to the caller (after its own argument checks),
+// which gets the bytes the solve needs.
 int fill_args(OTArgs& a, const fiode_odetrain_config* cfg, const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
-              const float* x_feat, void* workspace, size_t workspace_bytes) {
+              const float* x_feat, void* workspace, size_t workspace_bytes, int32_t activation = FIODE_ACT_RELU,
+              size_t* need = nullptr) {
+  if (const int rc = check_act(cfg, activation)) return rc;
   if (!cfg || !dyn || !w || !x_feat || !workspace) return FIODE_EINVAL;
   if (dyn->n_hidden != C || dyn->mlp_size != M || dyn->x_dim != FIODE_X) return FIODE_ESHAPE;
   if (dyn->qp_max_iter < 1 || dyn->qp_max_iter > 32) return FIODE_EINVAL;
@@ -1980,7 +2099,9 @@ int fill_args(OTArgs& a, const fiode_odetrain_config* cfg, const fiode_dyn_confi
   a.B = cfg->batch; a.niters = n; a.E = E; a.A = A; a.method = cfg->method;
   a.rtol = cfg->rtol; a.atol = cfg->atol; a.t0d = cfg->t0; a.t1d = cfg->t1;
   const OtLayout L = ot_layout(a.B, a.E, a.A);
-  if (workspace_bytes < L.total) return FIODE_EWORKSPACE;
+  const size_t total = L.total + (activation == FIODE_ACT_GROUPSORT ? gs_code_bytes(a.B, a.E) : 0);
+  if (need) *need = total;
+  else if (workspace_bytes < total) return FIODE_EWORKSPACE;
   a.t0 = (float)cfg->t0; a.t1 = (float)cfg->t1; a.hstep = (float)cfg->step_size;
   a.dropout_mode = dyn->dropout > 0.f ? cfg->dropout_mode : FIODE_DROPOUT_OFF;
   a.bit_mode = dyn->dropout == 0.5f;
@@ -2014,16 +2135,29 @@ int fill_args(OTArgs& a, const fiode_odetrain_config* cfg, const fiode_dyn_confi
   a.alog = reinterpret_cast<double*>(ws + L.alog);
   a.meta = reinterpret_cast<double*>(ws + L.meta);
   a.imeta = reinterpret_cast<int32_t*>(ws + L.imeta);
+  if (activation == FIODE_ACT_GROUPSORT) a.codes = reinterpret_cast<uint16_t*>(ws + L.total);     // (rk4: ys unused)
 #ifdef OT_PROFILE
   a.prof = reinterpret_cast<unsigned long long*>(ws + L.xs) + (size_t)OT_XRING * 2 * ((a.B + TR4 - 1) / TR4) * OT4_XSTRIDE + 8;
 #endif
   return FIODE_OK;
 }
 
+// Measuring hook (FIODE_DEBUG_OT_TILE16 set and not "0"): the ReLU solves take the 16-row kernels at
+// every B, so one build times them beside the 4-row ones and beside GroupSort.
+bool debug_ot_tile16() {
+  const char* e = getenv("FIODE_DEBUG_OT_TILE16");
+  return e && *e && *e != '0';
+}
+
 // the adjoint sweep (weight operands in registers: VjpW): rk4 k_ot_bwd, dopri5 k_odp_bwd
-hipError_t launch_sweep(const OTArgs& a, hipStream_t st) {
+hipError_t launch_sweep(const OTArgs& a, hipStream_t st, bool gs = false) {
   const dim3 grid((a.B + TR - 1) / TR);
-  const bool t4 = (a.B + TR4 - 1) / TR4 <= FIODE_OT4_MAX_TILES;
+  if (gs) {                   // GroupSort (rk4 only, fill_args): the 16-row sweep for every B
+    if (a.d.scale_nominal) hipLaunchKernelGGL((k_ot_bwd<true, GROUPSORT>), grid, dim3(256), sizeof(OtBwdShared), st, a);
+    else hipLaunchKernelGGL((k_ot_bwd<false, GROUPSORT>), grid, dim3(256), sizeof(OtBwdShared), st, a);
+    return hipGetLastError();
+  }
+  const bool t4 = (a.B + TR4 - 1) / TR4 <= FIODE_OT4_MAX_TILES && !debug_ot_tile16();
   const dim3 grid4((a.B + TR4 - 1) / TR4);
   if (a.method == FIODE_ODE_DOPRI5) {
     if (t4) {
@@ -2069,16 +2203,29 @@ extern "C" int fiode_odetrain_saved_offsets(const fiode_odetrain_config* cfg, in
   return FIODE_OK;
 }
 
-extern "C" int fiode_odetrain_forward(void* stream, const fiode_odetrain_config* cfg, const fiode_dyn_config* dyn,
-                                      const fiode_dyn_weights* w, const float* x_feat, const float* h0,
-                                      const uint8_t* masks, const uint64_t* offset_dev, float* y_out, int32_t* stats,
-                                      void* workspace, size_t workspace_bytes) {
+extern "C" size_t fiode_odetrain_workspace_bytes_act(const fiode_odetrain_config* cfg, int32_t activation) {
+  if (!cfg || cfg->batch <= 0 || check_act(cfg, activation)) return 0;
+  int E, A, n;
+  if (solve_shape(cfg, E, A, n) < 0) return 0;
+  return ot_layout(cfg->batch, E, A).total + (activation == FIODE_ACT_GROUPSORT ? gs_code_bytes(cfg->batch, E) : 0);
+}
+
+namespace {
+// The entry points' bodies.  args_first (the *_act symbols): every argument check runs before the
+// workspace-size check; the base symbols keep their order (fill_args' checks, the size, the rest).
+int ot_forward(void* stream, const fiode_odetrain_config* cfg, const fiode_dyn_config* dyn,
+               const fiode_dyn_weights* w, const float* x_feat, const float* h0, const uint8_t* masks,
+               const uint64_t* offset_dev, float* y_out, int32_t* stats, void* workspace, size_t workspace_bytes,
+               int32_t activation, bool args_first) {
   OTArgs a{};
   a.prio = (int)g_fiode_prio_mask;
-  int rc = fill_args(a, cfg, dyn, w, x_feat, workspace, workspace_bytes);
+  size_t need = 0;
+  int rc = fill_args(a, cfg, dyn, w, x_feat, workspace, workspace_bytes, activation, &need);
   if (rc) return rc;
+  if (!args_first && workspace_bytes < need) return FIODE_EWORKSPACE;
   if (!h0 || !y_out || !stats) return FIODE_EINVAL;
   if (a.dropout_mode == FIODE_DROPOUT_GIVEN && !masks) return FIODE_EINVAL;
+  if (workspace_bytes < need) return FIODE_EWORKSPACE;
   a.h0 = h0; a.masks = masks; a.offset_dev = offset_dev; a.y_out = y_out; a.stats = stats;
   a.drop_block = fiode_internal::debug_drop_publish();
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2094,20 +2241,41 @@ extern "C" int fiode_odetrain_forward(void* stream, const fiode_odetrain_config*
   const int nthreads = std::max(a.nslots, a.kw_pre * a.B);
   hipLaunchKernelGGL(k_ot_masks, dim3((nthreads + 255) / 256), dim3(256), 0, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
-  if (a.method == FIODE_ODE_DOPRI5) {
-    if ((a.B + TR4 - 1) / TR4 <= FIODE_OT4_MAX_TILES)
+  if (activation == FIODE_ACT_GROUPSORT) {
+    // GroupSort (rk4 only): the 16-row kernel for every B -- a sort pair is one lane's registers there
+    hipLaunchKernelGGL(k_ot_fwd<GROUPSORT>, dim3(ntiles), dim3(256), sizeof(OtShared), st, a);
+  } else if (a.method == FIODE_ODE_DOPRI5) {
+    if ((a.B + TR4 - 1) / TR4 <= FIODE_OT4_MAX_TILES && !debug_ot_tile16())
       hipLaunchKernelGGL(k_odp_fwd<true>, dim3((a.B + TR4 - 1) / TR4), dim3(256), sizeof(OdpShared<true>), st, a);
     else
       hipLaunchKernelGGL(k_odp_fwd<false>, dim3(ntiles), dim3(256), sizeof(OdpShared<false>), st, a);
-  } else if ((a.B + TR4 - 1) / TR4 <= FIODE_OT4_MAX_TILES) {
+  } else if ((a.B + TR4 - 1) / TR4 <= FIODE_OT4_MAX_TILES && !debug_ot_tile16()) {
     // 4-row tiles (tile4.h T4W: weights in registers)
     hipLaunchKernelGGL(k_ot_fwd4, dim3((a.B + TR4 - 1) / TR4), dim3(256), sizeof(OtShared4), st, a);
   } else {
     // the weights live in registers (tile16.h T16W)
-    hipLaunchKernelGGL(k_ot_fwd, dim3(ntiles), dim3(256), sizeof(OtShared), st, a);
+    hipLaunchKernelGGL(k_ot_fwd<RELU>, dim3(ntiles), dim3(256), sizeof(OtShared), st, a);
   }
   FIODE_HIP_CHECK(hipGetLastError());
   return FIODE_OK;
+}
+}  // namespace
+
+extern "C" int fiode_odetrain_forward(void* stream, const fiode_odetrain_config* cfg, const fiode_dyn_config* dyn,
+                                      const fiode_dyn_weights* w, const float* x_feat, const float* h0,
+                                      const uint8_t* masks, const uint64_t* offset_dev, float* y_out, int32_t* stats,
+                                      void* workspace, size_t workspace_bytes) {
+  return ot_forward(stream, cfg, dyn, w, x_feat, h0, masks, offset_dev, y_out, stats, workspace, workspace_bytes,
+                    FIODE_ACT_RELU, false);
+}
+
+extern "C" int fiode_odetrain_forward_act(void* stream, const fiode_odetrain_config* cfg,
+                                          const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
+                                          const float* x_feat, const float* h0, const uint8_t* masks,
+                                          const uint64_t* offset_dev, float* y_out, int32_t* stats, void* workspace,
+                                          size_t workspace_bytes, int32_t activation) {
+  return ot_forward(stream, cfg, dyn, w, x_feat, h0, masks, offset_dev, y_out, stats, workspace, workspace_bytes,
+                    activation, true);
 }
 
 namespace {
@@ -2138,22 +2306,44 @@ __global__ __launch_bounds__(M) void k_ot_gx(int E, const int32_t* __restrict__ 
 }
 }  // namespace
 
-extern "C" int fiode_odetrain_backward_x(void* stream, const fiode_odetrain_config* cfg, const fiode_dyn_config* dyn,
-                                         const fiode_dyn_weights* w, const float* x_feat, const float* g_y,
-                                         float* gx, const float* gx_add, const float* gx_add_scale, float* dbg_gft,
-                                         void* workspace, size_t workspace_bytes) {
+namespace {
+int ot_backward_x(void* stream, const fiode_odetrain_config* cfg, const fiode_dyn_config* dyn,
+                  const fiode_dyn_weights* w, const float* x_feat, const float* g_y, float* gx, const float* gx_add,
+                  const float* gx_add_scale, float* dbg_gft, void* workspace, size_t workspace_bytes,
+                  int32_t activation, bool args_first) {
   OTArgs a{};
   a.prio = (int)g_fiode_prio_mask;
-  int rc = fill_args(a, cfg, dyn, w, x_feat, workspace, workspace_bytes);
+  size_t need = 0;
+  int rc = fill_args(a, cfg, dyn, w, x_feat, workspace, workspace_bytes, activation, &need);
   if (rc) return rc;
+  if (!args_first && workspace_bytes < need) return FIODE_EWORKSPACE;
   if (!g_y || !gx || (gx_add && !gx_add_scale)) return FIODE_EINVAL;
+  if (workspace_bytes < need) return FIODE_EWORKSPACE;
   a.g_y = g_y; a.dbg_gft = dbg_gft;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  FIODE_HIP_CHECK(launch_sweep(a, st));
+  FIODE_HIP_CHECK(launch_sweep(a, st, activation == FIODE_ACT_GROUPSORT));
   hipLaunchKernelGGL(k_ot_gx, dim3(a.B), dim3(M), 0, st, a.E, a.method == FIODE_ODE_DOPRI5 ? (const int32_t*)a.imeta : nullptr,
                      (const float*)a.gz1, w->Qx, gx_add, gx_add_scale, gx);
   FIODE_HIP_CHECK(hipGetLastError());
   return FIODE_OK;
+}
+}  // namespace
+
+extern "C" int fiode_odetrain_backward_x(void* stream, const fiode_odetrain_config* cfg, const fiode_dyn_config* dyn,
+                                         const fiode_dyn_weights* w, const float* x_feat, const float* g_y,
+                                         float* gx, const float* gx_add, const float* gx_add_scale, float* dbg_gft,
+                                         void* workspace, size_t workspace_bytes) {
+  return ot_backward_x(stream, cfg, dyn, w, x_feat, g_y, gx, gx_add, gx_add_scale, dbg_gft, workspace,
+                       workspace_bytes, FIODE_ACT_RELU, false);
+}
+
+extern "C" int fiode_odetrain_backward_x_act(void* stream, const fiode_odetrain_config* cfg,
+                                             const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
+                                             const float* x_feat, const float* g_y, float* gx, const float* gx_add,
+                                             const float* gx_add_scale, float* dbg_gft, void* workspace,
+                                             size_t workspace_bytes, int32_t activation) {
+  return ot_backward_x(stream, cfg, dyn, w, x_feat, g_y, gx, gx_add, gx_add_scale, dbg_gft, workspace,
+                       workspace_bytes, activation, true);
 }
 
 extern "C" int fiode_odetrain_backward_weights(void* stream, const fiode_odetrain_config* cfg,
@@ -2178,23 +2368,26 @@ extern "C" int fiode_odetrain_backward_weights(void* stream, const fiode_odetrai
   return fiode_internal::launch_wgrad(static_cast<hipStream_t>(stream), io);
 }
 
-extern "C" int fiode_odetrain_backward(void* stream, const fiode_odetrain_config* cfg, const fiode_dyn_config* dyn,
-                                       const fiode_dyn_weights* w, const float* x_feat, const float* g_y,
-                                       fiode_lyap_grads* grads, float* dbg_gft, void* workspace,
-                                       size_t workspace_bytes) {
+namespace {
+int ot_backward(void* stream, const fiode_odetrain_config* cfg, const fiode_dyn_config* dyn,
+                const fiode_dyn_weights* w, const float* x_feat, const float* g_y, fiode_lyap_grads* grads,
+                float* dbg_gft, void* workspace, size_t workspace_bytes, int32_t activation, bool args_first) {
   // the adjoint sweep, then the weight-gradient chain whose last kernel also forms dL/dx_feat (from
   // the per-image g_u it reduces): one launch fewer than _x + _weights (k_ot_gx), so the x-gradient
   // may differ from fiode_odetrain_backward_x's in the last bits (summation order of g_u)
   OTArgs a{};
   a.prio = (int)g_fiode_prio_mask;
-  int rc = fill_args(a, cfg, dyn, w, x_feat, workspace, workspace_bytes);
+  size_t need = 0;
+  int rc = fill_args(a, cfg, dyn, w, x_feat, workspace, workspace_bytes, activation, &need);
   if (rc) return rc;
+  if (!args_first && workspace_bytes < need) return FIODE_EWORKSPACE;
   if (!g_y || !grads || !grads->Q1 || !grads->b1 || !grads->Qx || !grads->bx || !grads->Q2 || !grads->b2 ||
       !grads->Q3 || !grads->b3 || !grads->x_feat)
     return FIODE_EINVAL;
+  if (workspace_bytes < need) return FIODE_EWORKSPACE;
   a.g_y = g_y; a.dbg_gft = dbg_gft;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  FIODE_HIP_CHECK(launch_sweep(a, st));
+  FIODE_HIP_CHECK(launch_sweep(a, st, activation == FIODE_ACT_GROUPSORT));
   const OtLayout L = ot_layout(a.B, a.E, a.A);
   fiode_internal::WgradIO io{};
   io.B = a.B; io.S = a.E; io.x_feat = x_feat; io.Qx = w->Qx; io.h = a.hs; io.a1 = a.a1; io.a2 = a.a2;
@@ -2203,6 +2396,23 @@ extern "C" int fiode_odetrain_backward(void* stream, const fiode_odetrain_config
   io.workspace = static_cast<char*>(workspace) + L.wg;
   io.grads = *grads;
   return fiode_internal::launch_wgrad(st, io);
+}
+}  // namespace
+
+extern "C" int fiode_odetrain_backward(void* stream, const fiode_odetrain_config* cfg, const fiode_dyn_config* dyn,
+                                       const fiode_dyn_weights* w, const float* x_feat, const float* g_y,
+                                       fiode_lyap_grads* grads, float* dbg_gft, void* workspace,
+                                       size_t workspace_bytes) {
+  return ot_backward(stream, cfg, dyn, w, x_feat, g_y, grads, dbg_gft, workspace, workspace_bytes, FIODE_ACT_RELU,
+                     false);
+}
+
+extern "C" int fiode_odetrain_backward_act(void* stream, const fiode_odetrain_config* cfg,
+                                           const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
+                                           const float* x_feat, const float* g_y, fiode_lyap_grads* grads,
+                                           float* dbg_gft, void* workspace, size_t workspace_bytes,
+                                           int32_t activation) {
+  return ot_backward(stream, cfg, dyn, w, x_feat, g_y, grads, dbg_gft, workspace, workspace_bytes, activation, true);
 }
 
 // ---- the train_ode loss term: F.nll_loss(torch.log(y_hat), y) (pl_modules.py:494-497) --------

@@ -42,6 +42,38 @@ __device__ __forceinline__ void dropout_relu16(f32x4v& z, uint32_t w, int hb, in
     z[r] = keep ? fmaxf(z[r] * scale, 0.f) : 0.f;
   }
 }
+// GroupSort(dropout(z)) of one pair block in train mode, in three steps.  x / y hold the units
+// (u, u + 64), this lane's 4 of each.  dropout4: d = keep ? z * scale : 0 (keep bits 0..3 of k).
+// pair_code4 (of the dropped values, for the backward): bit r = dx > dy (the first member held the
+// larger value), bit 4 + r = dx == dy (a tie; two dropped members are one).  sort4: x <- max, y <- min.
+__device__ __forceinline__ void dropout4(f32x4v& z, uint32_t k, float scale) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) z[r] = ((k >> r) & 1u) ? z[r] * scale : 0.f;
+}
+__device__ __forceinline__ uint32_t pair_code4(const f32x4v& x, const f32x4v& y) {
+  uint32_t code = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    code |= (x[r] > y[r] ? 1u : 0u) << r;
+    code |= (x[r] == y[r] ? 1u : 0u) << (4 + r);
+  }
+  return code;
+}
+__device__ __forceinline__ void sort4(f32x4v& x, f32x4v& y) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float a = x[r], b = y[r];
+    x[r] = fmaxf(a, b);
+    y[r] = fminf(a, b);
+  }
+}
+// The keep bits of part p's GroupSort blocks out of one layer's 4 keep words kw (bit t of word i =
+// unit 32 i + t): block p (units 16p .. 16p + 15, word p >> 1 at bit 16 (p & 1)) in bits 0..15, its
+// partners (block p + 4, word 2 + (p >> 1)) in bits 16..31.
+__device__ __forceinline__ uint32_t gs_keep16(const uint32_t* kw, int p) {
+  const int sh = 16 * (p & 1);
+  return ((kw[p >> 1] >> sh) & 0xFFFFu) | ((kw[2 + (p >> 1)] >> sh) << 16);
+}
 __device__ __forceinline__ float sel4(const float (&v)[C], int s, int q) {   // v[4s + q], 0 past C
   const int k = 4 * s + q;
   float x = 0.f;
@@ -338,15 +370,23 @@ __device__ __forceinline__ void l1_pair(const T16W& w, const f32x4v (&uacc)[8], 
 // kShareL1 (z1x: LDS [8][64][4], all 4 waves call with the same choice): layer 1 split over the
 // waves -- wave p computes blocks 2p, 2p+1 (6 MFMA instead of 24), they meet in LDS behind one
 // workgroup barrier and every wave reads the 8 blocks back; bit-identical to the replicated layer 1.
-// A = GROUPSORT (eval mode: masks and scale ignored, nothing saved, layer 1 replicated): layer 1's
+// A = GROUPSORT (without kTrain, eval mode: masks and scale ignored, nothing saved; layer 1 replicated): layer 1's
 // pair (u, u + 64) is blocks (hb, hb + 4), which every wave holds; layer 2's is the wave's own two
 // output blocks (p, p + 4; w from load_t16w<GROUPSORT>): both sorts are lane-local, no barrier.
-template <bool kShareL1 = false, Act A = RELU>
+// A = GROUPSORT with kTrain (the train_ode solve): a = GroupSort(dropout(z)) per hidden layer, d =
+// keep ? z * scale : 0 and then the sort of the pairs (u, u + 64).  kw2p: the layer-2 keep bits of
+// the wave's own blocks, block p's 16 units in bits 0..15 and block p + 4's in bits 16..31
+// (gs_keep16).  Part p stores blocks p and p + 4 of the post-sort a1 / a2 (unit-indexed rows, as
+// ReLU's) and, to coderow (nullable; 16 uint16 per (row, eval)), the pair codes of pair block p:
+// coderow[4 p + q] = layer 1's code byte (pair_code4) | layer 2's << 8, i.e. pair u of
+// layer l is bit (u & 3) (order) and bit 4 + (u & 3) (tie) of byte 2 (u >> 2) + l.
+template <bool kShareL1 = false, Act A = RELU, bool kTrain = false>
 __device__ __forceinline__ void mlp16_part(const T16W& w, const f32x4v (&uacc)[8], const float (&h)[C],
                                            const uint32_t (&kw1)[4], uint32_t kw2p, float scale, int p, int q,
                                            float* a1row, float* a2row, float* zpart_lane,
-                                           float (*z1x)[64][4] = nullptr) {
-  static_assert(A == RELU || !kShareL1, "GroupSort: eval mode, layer 1 replicated on every wave");
+                                           float (*z1x)[64][4] = nullptr, uint16_t* coderow = nullptr) {
+  static_assert(A == RELU || !kShareL1, "GroupSort: layer 1 replicated on every wave");
+  uint32_t code = 0;          // GROUPSORT, kTrain: the pair codes of pair block p, both layers
   f32x4v z1[8];
   if constexpr (kShareL1) {
     const int lane = threadIdx.x & 63;
@@ -371,7 +411,22 @@ __device__ __forceinline__ void mlp16_part(const T16W& w, const f32x4v (&uacc)[8
 #pragma unroll
       for (int hb = 0; hb < 8; ++hb) z1[hb] = mfma16(w.q1[hb][s], bs, z1[hb]);
     }
-    if constexpr (A == GROUPSORT) {
+    if constexpr (A == GROUPSORT && kTrain) {
+#pragma unroll
+      for (int hb = 0; hb < 4; ++hb) {
+        // units 16 hb + 4q + r and their partners 64 + ..: words hb >> 1 and 2 + (hb >> 1), same bits
+        const int sh = 16 * (hb & 1) + 4 * q;
+        dropout4(z1[hb], kw1[hb >> 1] >> sh, scale);
+        dropout4(z1[hb + 4], kw1[2 + (hb >> 1)] >> sh, scale);
+        if (hb == p) code = pair_code4(z1[hb], z1[hb + 4]);       // wave-uniform: this part's pair block
+        sort4(z1[hb], z1[hb + 4]);
+        if (hb == p && a1row) {
+          *reinterpret_cast<f32x4*>(a1row + 16 * hb + 4 * q) = f32x4{z1[hb][0], z1[hb][1], z1[hb][2], z1[hb][3]};
+          *reinterpret_cast<f32x4*>(a1row + 16 * (hb + 4) + 4 * q) =
+              f32x4{z1[hb + 4][0], z1[hb + 4][1], z1[hb + 4][2], z1[hb + 4][3]};
+        }
+      }
+    } else if constexpr (A == GROUPSORT) {
 #pragma unroll
       for (int hb = 0; hb < 4; ++hb)
 #pragma unroll
@@ -402,7 +457,18 @@ __device__ __forceinline__ void mlp16_part(const T16W& w, const f32x4v (&uacc)[8
       for (int t = 0; t < 4; ++t) z2[o] = mfma16(w.q2[o][hb][t], z1[hb][t], z2[o]);
     }
   }
-  if constexpr (A == GROUPSORT) {
+  if constexpr (A == GROUPSORT && kTrain) {
+    dropout4(z2[0], kw2p >> (4 * q), scale);
+    dropout4(z2[1], kw2p >> (16 + 4 * q), scale);
+    code |= pair_code4(z2[0], z2[1]) << 8;
+    sort4(z2[0], z2[1]);
+    if (a2row) {
+#pragma unroll
+      for (int o = 0; o < 2; ++o)
+        *reinterpret_cast<f32x4*>(a2row + 16 * (p + 4 * o) + 4 * q) = f32x4{z2[o][0], z2[o][1], z2[o][2], z2[o][3]};
+    }
+    if (coderow) coderow[4 * p + q] = (uint16_t)code;
+  } else if constexpr (A == GROUPSORT) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float x = z2[0][r], y = z2[1][r];

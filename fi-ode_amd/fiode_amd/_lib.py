@@ -212,6 +212,16 @@ def _load():
         "fiode_odetrain_backward_weights": (ct.c_int, [_vp, ct.POINTER(OdeTrainConfig), ct.POINTER(DynConfig),
                                                        ct.POINTER(DynWeights), _vp, ct.POINTER(LyapGrads), _vp,
                                                        ct.c_size_t]),
+        "fiode_odetrain_workspace_bytes_act": (ct.c_size_t, [ct.POINTER(OdeTrainConfig), ct.c_int32]),
+        "fiode_odetrain_forward_act": (ct.c_int, [_vp, ct.POINTER(OdeTrainConfig), ct.POINTER(DynConfig),
+                                                  ct.POINTER(DynWeights), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  ct.c_size_t, ct.c_int32]),
+        "fiode_odetrain_backward_act": (ct.c_int, [_vp, ct.POINTER(OdeTrainConfig), ct.POINTER(DynConfig),
+                                                   ct.POINTER(DynWeights), _vp, _vp, ct.POINTER(LyapGrads), _vp, _vp,
+                                                   ct.c_size_t, ct.c_int32]),
+        "fiode_odetrain_backward_x_act": (ct.c_int, [_vp, ct.POINTER(OdeTrainConfig), ct.POINTER(DynConfig),
+                                                     ct.POINTER(DynWeights), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                     ct.c_size_t, ct.c_int32]),
         "fiode_groupsort_forward": (ct.c_int, [_vp, ct.c_int64, ct.c_int64, ct.c_int64, _vp, _vp]),
         "fiode_groupsort_backward": (ct.c_int, [_vp, ct.c_int64, ct.c_int64, ct.c_int64, _vp, _vp, _vp]),
         "fiode_head_out": (ct.c_int, [_vp, ct.c_int32, ct.c_int32, ct.c_int32, _vp, _vp, _vp, _vp]),

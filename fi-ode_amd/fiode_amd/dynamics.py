@@ -11,9 +11,11 @@ through ``_EvalDotFn``, whose backward is the fused HIP vector-Jacobian product
 ``effective_weights()``' own autograd (the Cayley maps).  One derivative only: a double backward
 raises.  The training-mode eval_dot with dropout is fused, with its backward, into the Lyapunov
 step and the train_ode solve (``fiode_amd.lyapunov``).  The Lyapunov step implements both
-activations, GroupSort behind the opt-in switch ``ops.GROUPSORT_TRAINING``; the train_ode solves
-implement 'ReLU' only.  Training a GroupSort module raises NotImplementedError with the switch off,
-and with it on once the train_ode branch is active.
+activations, GroupSort behind the opt-in switch ``ops.GROUPSORT_TRAINING``; so does the rk4
+train_ode solve, GroupSort behind the second switch ``ops.GROUPSORT_TRAIN_ODE`` (on the 16-row-tile
+kernels for every batch size); the dopri5 train_ode solve implements 'ReLU' only.  Training a
+GroupSort module raises NotImplementedError with the switches off; with only the first on, once the
+train_ode branch is active; with both on, only when ``train_ode_solver`` is 'dopri5'.
 """
 from __future__ import annotations
 
@@ -81,8 +83,8 @@ class OrthoClassDynProjectSimplexLips(nn.Module):
         elif activation == "GroupSort":
             # classification.py:44-48 (the reference's config default): no parameters or buffers, so
             # the state_dict keys are the ReLU module's.  Evaluation, ODE solves, certification and,
-            # with ops.GROUPSORT_TRAINING on, the Lyapunov training step; the train_ode solves
-            # refuse it (ops.require_relu)
+            # with ops.GROUPSORT_TRAINING on, the Lyapunov training step; with ops.GROUPSORT_TRAIN_ODE
+            # on, the rk4 train_ode solve; the dopri5 train_ode solve refuses it (ops.require_relu)
             self.activation = GroupSort()
         else:
             raise NotImplementedError(f"activation {activation!r}: the fused dynamics kernels implement 'ReLU' "

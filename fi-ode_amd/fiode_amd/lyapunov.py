@@ -693,8 +693,11 @@ class LyapunovLearning(nn.Module):
         ``ops.GROUPSORT_TRAINING`` is on: a module whose dynamics use another activation must not
         reach a kernel that does not implement it -- NotImplementedError, before any tensor is
         touched.  ``step``: the caller runs a training step (the Lyapunov step, and the solve only
-        when the train_ode branch is active); else it is about the solve itself."""
-        ops.require_relu(self.dyn_fun.dyn_cfg(), what, lyap_only=step and not self.ode_branch_active())
+        when the train_ode branch is active); else it is about the solve itself.  With
+        ``ops.GROUPSORT_TRAIN_ODE`` on, GroupSort also passes where the solve is the rk4 one
+        (``train_ode_solver='rk4'``); 'dopri5' keeps refusing."""
+        ops.require_relu(self.dyn_fun.dyn_cfg(), what, lyap_only=step and not self.ode_branch_active(),
+                         ode_rk4=self.train_ode_solver == "rk4")
 
     def ode_plan(self, batch: int, masks: Optional[torch.Tensor] = None) -> dict:
         """Solver plan of the train_ode solve (make_solver_params(train_ode_solver, train_ode_tol),

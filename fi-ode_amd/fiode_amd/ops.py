@@ -60,7 +60,7 @@ TRAIN_RELU_ONLY = ("{what}: GroupSort dynamics are supported for evaluation, ODE
 # FIODE_ACT_GROUPSORT: a = GroupSort(dropout(z)), forward and backward).  Off: every training path
 # refuses a GroupSort DynCfg as before.  On: ``lyap_step`` (and with it LyapunovLearning.compute_loss
 # and GraphTrainStep while the train_ode branch is not active) takes it; the train_ode solves
-# (``odetrain_*``, LyapunovLearning.ode_plan) keep refusing -- their kernels are ReLU-only.
+# (``odetrain_*``, LyapunovLearning.ode_plan) keep refusing unless GROUPSORT_TRAIN_ODE (below) is on.
 GROUPSORT_TRAINING = False
 
 
@@ -76,15 +76,47 @@ def groupsort_training(on: bool = True):
         GROUPSORT_TRAINING = before
 
 
-def require_relu(dyn: DynCfg, what: str, lyap_only: bool = False) -> None:
+# Second opt-in, on top of GROUPSORT_TRAINING: GroupSort through the rk4 train_ode solve
+# (fiode_odetrain_*_act with FIODE_ACT_GROUPSORT, the 16-row-tile kernels for every batch size).
+# Off: every path, message and return value is as without it.  On: ``odetrain_*`` take a GroupSort
+# DynCfg when the config's method is rk4, and LyapunovLearning (ode_plan, compute_loss with the
+# train_ode branch active, GraphTrainStep) and the TrajectorySampler's train-mode rk4 path follow;
+# the dopri5 solve keeps refusing.
+GROUPSORT_TRAIN_ODE = False
+
+
+@contextlib.contextmanager
+def groupsort_train_ode(on: bool = True):
+    """Inside: ``GROUPSORT_TRAIN_ODE = on`` and, when on, ``GROUPSORT_TRAINING`` too (a step with the
+    train_ode branch active also runs the fused Lyapunov step); both earlier values are back on exit,
+    after an exception too."""
+    global GROUPSORT_TRAIN_ODE, GROUPSORT_TRAINING
+    before = (GROUPSORT_TRAIN_ODE, GROUPSORT_TRAINING)
+    GROUPSORT_TRAIN_ODE = bool(on)
+    GROUPSORT_TRAINING = GROUPSORT_TRAINING or bool(on)
+    try:
+        yield
+    finally:
+        GROUPSORT_TRAIN_ODE, GROUPSORT_TRAINING = before
+
+
+def require_relu(dyn: DynCfg, what: str, lyap_only: bool = False, ode_rk4: bool = False) -> None:
     """The one gate of the training kernels: refuse an activation they do not implement before
-    anything is launched.  ReLU passes everywhere.  GroupSort passes only with ``lyap_only`` (the
-    caller launches the fused Lyapunov step and no train_ode solve) while GROUPSORT_TRAINING is on."""
+    anything is launched.  ReLU passes everywhere.  GroupSort passes with ``lyap_only`` (the caller
+    launches the fused Lyapunov step and no train_ode solve) while GROUPSORT_TRAINING is on, and with
+    ``ode_rk4`` (the train_ode solve the caller launches, alone or beside the Lyapunov step, is the
+    rk4 one) while GROUPSORT_TRAIN_ODE is on."""
     if dyn.activation == "ReLU":
         return
     if lyap_only and GROUPSORT_TRAINING and dyn.activation == "GroupSort":
         return
+    if ode_rk4 and GROUPSORT_TRAIN_ODE and dyn.activation == "GroupSort":
+        return
     raise NotImplementedError(TRAIN_RELU_ONLY.format(what=what))
+
+
+def _is_rk4(cfg) -> bool:
+    return getattr(cfg, "method", None) == L.FIODE_ODE_RK4
 
 
 def _stream(dev: torch.device) -> ct.c_void_p:
@@ -591,7 +623,8 @@ def odetrain_forward(x_feat: torch.Tensor, h0: torch.Tensor, weights: Dict[str, 
                      offset_dev: Optional[torch.Tensor] = None):
     """fiode_odetrain_forward: y(t1) of the train-mode RK4 solve.  Returns (y [B,C], stats int32[8],
     workspace) -- the workspace carries the saved activations to ``odetrain_backward``."""
-    require_relu(dyn, "odetrain_forward")
+    require_relu(dyn, "odetrain_forward", ode_rk4=_is_rk4(cfg))
+    act = _act(dyn)
     dev = h0.device
     B = int(cfg.batch)
     if B > L.FIODE_ODE_MAX_BATCH:
@@ -606,15 +639,15 @@ def odetrain_forward(x_feat: torch.Tensor, h0: torch.Tensor, weights: Dict[str, 
     if offset_dev is not None:
         offset_dev = _need(offset_dev, "offset_dev", (1,), torch.int64, dev)
     lib = L.lib()
-    ws = torch.empty(lib.fiode_odetrain_workspace_bytes(ct.byref(cfg)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(lib.fiode_odetrain_workspace_bytes_act(ct.byref(cfg), act), dtype=torch.uint8, device=dev)
     ws_w, cw = _weights_c(weights, dev)
     y = torch.empty((B, C), dtype=torch.float32, device=dev)
     # k_ot_masks zeroes the stats words itself (a zero fill here ran on the chain ahead of the solve)
     stats = torch.empty(8, dtype=torch.int32, device=dev)
     dc = dyn.to_c()
-    rc = lib.fiode_odetrain_forward(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), x_feat.data_ptr(),
-                                    h0.data_ptr(), _ptr(masks), _ptr(offset_dev), y.data_ptr(), stats.data_ptr(),
-                                    ws.data_ptr(), ws.numel())
+    rc = lib.fiode_odetrain_forward_act(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), x_feat.data_ptr(),
+                                        h0.data_ptr(), _ptr(masks), _ptr(offset_dev), y.data_ptr(),
+                                        stats.data_ptr(), ws.data_ptr(), ws.numel(), act)
     L.check(rc, "fiode_odetrain_forward")
     del ws_w
     return y, stats, ws
@@ -650,10 +683,28 @@ def odetrain_status_word(ws: torch.Tensor, cfg: L.OdeTrainConfig) -> torch.Tenso
     return ws[off[12]:off[12] + 4].view(torch.int32)
 
 
+def odetrain_pair_codes(ws: torch.Tensor, cfg: L.OdeTrainConfig) -> Dict[str, torch.Tensor]:
+    """The GroupSort pair codes a forward saved in its workspace (for checkers), decoded to bool
+    tensors [B, E, 2, 64] (row, eval, hidden layer, pair u = units (u, u + 64)): ``order`` = the first
+    member's dropped value was the larger one, ``tie`` = the two were equal (two dropped members are a
+    tie).  The region starts at fiode_odetrain_workspace_bytes(cfg), behind the ReLU layout."""
+    B, E = int(cfg.batch), odetrain_evals(cfg)
+    lib = L.lib()
+    start = lib.fiode_odetrain_workspace_bytes(ct.byref(cfg))
+    if lib.fiode_odetrain_workspace_bytes_act(ct.byref(cfg), L.FIODE_ACT_GROUPSORT) == 0 or \
+            ws.numel() < start + B * E * 32:
+        raise ValueError("odetrain_pair_codes: not the workspace of a GroupSort rk4 solve of this config")
+    by = ws[start:start + B * E * 32].view(B, E, 16, 2).permute(0, 1, 3, 2).to(torch.int32)      # [B, E, layer, u >> 2]
+    sh = torch.arange(4, device=ws.device, dtype=torch.int32)
+    order = ((by[..., None] >> sh) & 1).reshape(B, E, 2, 64).bool()
+    tie = ((by[..., None] >> (sh + 4)) & 1).reshape(B, E, 2, 64).bool()
+    return dict(order=order, tie=tie)
+
+
 def odetrain_backward(g_y: torch.Tensor, x_feat: torch.Tensor, weights: Dict[str, torch.Tensor], dyn: DynCfg,
                       cfg: L.OdeTrainConfig, ws: torch.Tensor, debug: bool = False):
     """fiode_odetrain_backward: dL/d(weights, x_feat) from dL/dy(t1).  Returns (grads, dbg_gft)."""
-    require_relu(dyn, "odetrain_backward")
+    require_relu(dyn, "odetrain_backward", ode_rk4=_is_rk4(cfg))
     dev = g_y.device
     B = int(cfg.batch)
     g_y = _need(g_y.float(), "g_y", (B, C), torch.float32, dev)
@@ -665,8 +716,9 @@ def odetrain_backward(g_y: torch.Tensor, x_feat: torch.Tensor, weights: Dict[str
     cg = L.LyapGrads(*[grads[k].data_ptr() for k in WEIGHT_KEYS + ("x_feat",)])
     dbg = torch.empty((B, E, C), dtype=torch.float32, device=dev) if debug else None
     dc = dyn.to_c()
-    rc = L.lib().fiode_odetrain_backward(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), x_feat.data_ptr(),
-                                         g_y.data_ptr(), ct.byref(cg), _ptr(dbg), ws.data_ptr(), ws.numel())
+    rc = L.lib().fiode_odetrain_backward_act(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw),
+                                             x_feat.data_ptr(), g_y.data_ptr(), ct.byref(cg), _ptr(dbg),
+                                             ws.data_ptr(), ws.numel(), _act(dyn))
     L.check(rc, "fiode_odetrain_backward")
     del ws_w
     return grads, dbg
@@ -677,7 +729,7 @@ def odetrain_backward_x(g_y: torch.Tensor, x_feat: torch.Tensor, weights: Dict[s
                         gx_add_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fiode_odetrain_backward_x: the adjoint sweep and dL/dx_feat [B, X] (+ gx_add * gx_add_scale,
     a device scalar).  ``odetrain_backward_weights`` on the same workspace completes the gradients."""
-    require_relu(dyn, "odetrain_backward_x")
+    require_relu(dyn, "odetrain_backward_x", ode_rk4=_is_rk4(cfg))
     dev = g_y.device
     B = int(cfg.batch)
     g_y = _need(g_y.float(), "g_y", (B, C), torch.float32, dev)
@@ -688,10 +740,10 @@ def odetrain_backward_x(g_y: torch.Tensor, x_feat: torch.Tensor, weights: Dict[s
     ws_w, cw = _weights_c(weights, dev)
     gx = torch.empty((B, X), dtype=torch.float32, device=dev)
     dc = dyn.to_c()
-    rc = L.lib().fiode_odetrain_backward_x(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), x_feat.data_ptr(),
-                                           g_y.data_ptr(), gx.data_ptr(), _ptr(gx_add),
-                                           _ptr(gx_add_scale if gx_add is not None else None), None, ws.data_ptr(),
-                                           ws.numel())
+    rc = L.lib().fiode_odetrain_backward_x_act(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw),
+                                               x_feat.data_ptr(), g_y.data_ptr(), gx.data_ptr(), _ptr(gx_add),
+                                               _ptr(gx_add_scale if gx_add is not None else None), None,
+                                               ws.data_ptr(), ws.numel(), _act(dyn))
     L.check(rc, "fiode_odetrain_backward_x")
     del ws_w
     return gx
@@ -700,7 +752,7 @@ def odetrain_backward_x(g_y: torch.Tensor, x_feat: torch.Tensor, weights: Dict[s
 def odetrain_backward_weights(x_feat: torch.Tensor, weights: Dict[str, torch.Tensor], dyn: DynCfg,
                               cfg: L.OdeTrainConfig, ws: torch.Tensor) -> Dict[str, torch.Tensor]:
     """fiode_odetrain_backward_weights: the eight weight gradients (after odetrain_backward_x)."""
-    require_relu(dyn, "odetrain_backward_weights")
+    require_relu(dyn, "odetrain_backward_weights", ode_rk4=_is_rk4(cfg))
     dev = x_feat.device
     B = int(cfg.batch)
     x_feat = _need(x_feat, "x_feat", (B, X), torch.float32, dev)

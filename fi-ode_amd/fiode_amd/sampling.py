@@ -104,7 +104,8 @@ class TrajectorySampler(AbstractSampler):
     train-mode solve ``fiode_odetrain_forward`` (fresh Philox dropout masks per f-eval, as the
     reference's dropout draws fresh masks per call), whose saved stage-1 inputs are the grid states,
     then torchdiffeq's FixedGridODESolver linear interpolation to the n output times.  A train-mode
-    adaptive solve with dropout is not fused and raises."""
+    adaptive solve with dropout is not fused and raises.  GroupSort dynamics take the train-mode rk4
+    path inside ``ops.groupsort_train_ode()`` (the gate of ``ops.odetrain_forward``)."""
 
     TRAJ_SEED_SALT = 0x7A5C_3E11       # decorrelates its dropout masks from the train_ode solve's
 

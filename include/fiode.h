@@ -173,8 +173,8 @@ FIODE_API int fiode_dyn_eval(void* stream, const fiode_dyn_config* dyn, const fi
  * on an error.  FIODE_ABI_VERSION does not move for them: they are new symbols only, and the
  * structs, the existing prototypes and their behaviour are unchanged, so a caller built against
  * ABI 5 before they existed still binds and runs as before.  Of the training entry points,
- * the fused Lyapunov step has both activations (fiode_lyap_step_act below); the train_ode solves
- * (fiode_odetrain_*) implement ReLU only. */
+ * the fused Lyapunov step has both activations (fiode_lyap_step_act below), and so has the rk4
+ * train_ode solve (fiode_odetrain_*_act below); the dopri5 train_ode solve implements ReLU only. */
 enum { FIODE_ACT_RELU = 0, FIODE_ACT_GROUPSORT = 1 };
 FIODE_API int fiode_dyn_eval_act(void* stream, const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
                                  int32_t batch, int32_t rows_per_image, const float* x_feat, const float* h,
@@ -205,7 +205,7 @@ FIODE_API int fiode_lyap_step_act(void* stream, const fiode_lyap_config* cfg, co
  * minimum).  dbg (nullable): optional per-row outputs, NULL members are not written.  Argument
  * checks, error codes and batch == 0 as fiode_dyn_eval_act.  With this, the eval-mode dynamics are
  * differentiable outside the training entry points (fiode_lyap_step[_act], fiode_odetrain_*), which
- * keep their own fused backward with dropout (fiode_odetrain_*: ReLU only). */
+ * keep their own fused backward with dropout (fiode_odetrain_*_act: GroupSort for rk4 only). */
 typedef struct fiode_dyn_eval_debug {
   float* f;              /* [N][C] the recomputed eval_dot (bit-equal to the forward's)           */
   float* qp_lower;       /* [N][C] QP lower bound                                                 */
@@ -391,6 +391,42 @@ FIODE_API int fiode_odetrain_backward_weights(void* stream, const fiode_odetrain
                                               const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
                                               const float* x_feat, fiode_lyap_grads* grads, void* workspace,
                                               size_t workspace_bytes);
+
+/* The train_ode solve with the activation of the dynamics MLP: the base entry points' arguments
+ * followed by the activation, and the base entry points are their FIODE_ACT_RELU case bit for bit
+ * (same kernels, same workspace layout and size, FIODE_ODETRAIN_NSAVED and the saved offsets).  New
+ * symbols only: FIODE_ABI_VERSION does not move.  Another activation is FIODE_EINVAL; FIODE_ACT_GROUPSORT
+ * with method FIODE_ODE_DOPRI5 is FIODE_ESHAPE (not implemented); every argument check runs before
+ * the workspace-size check and nothing is launched on an error.
+ * FIODE_ACT_GROUPSORT (FIODE_ODE_RK4): every eval applies a = GroupSort(dropout(z)) per hidden layer,
+ * the rule of fiode_lyap_step_act above, forward and backward.  The solve and its sweep run on the
+ * 16-row-tile kernels for every B <= FIODE_ODE_MAX_BATCH (ceil(B / 16) co-resident workgroups): there
+ * one wave holds hidden blocks p and p + 4, so both members of a sort pair (u, u + M/2) are one lane's
+ * registers.  The saved a1 / a2 rows ([5], [6]) are the post-sort activations, unit-indexed as ReLU's.
+ * The backward cannot tell a pair's order from them, so the forward also saves pair codes, in a region
+ * appended to the workspace: it starts at byte fiode_odetrain_workspace_bytes(cfg) and holds, per row
+ * (b, e), 32 bytes; pair u (0 .. M/2 - 1) of hidden layer l (0, 1) is byte 2 (u >> 2) + l, bit (u & 3)
+ * = "d[u] > d[u + M/2]" and bit 4 + (u & 3) = "d[u] == d[u + M/2]" (a tie; two dropped members are
+ * one).  fiode_odetrain_workspace_bytes_act gives the total (0 for an invalid cfg or an activation
+ * the solve does not implement).  A sweep reads the codes and the keep words and writes neither, so
+ * it may be repeated on one forward's workspace.  fiode_odetrain_backward_weights reads only arrays
+ * that do not depend on the activation: it has no twin and takes either workspace. */
+FIODE_API size_t fiode_odetrain_workspace_bytes_act(const fiode_odetrain_config* cfg, int32_t activation);
+FIODE_API int fiode_odetrain_forward_act(void* stream, const fiode_odetrain_config* cfg,
+                                         const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
+                                         const float* x_feat, const float* h0, const uint8_t* masks,
+                                         const uint64_t* offset_dev, float* y_out, int32_t* stats, void* workspace,
+                                         size_t workspace_bytes, int32_t activation);
+FIODE_API int fiode_odetrain_backward_act(void* stream, const fiode_odetrain_config* cfg,
+                                          const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
+                                          const float* x_feat, const float* g_y, fiode_lyap_grads* grads,
+                                          float* dbg_gft, void* workspace, size_t workspace_bytes,
+                                          int32_t activation);
+FIODE_API int fiode_odetrain_backward_x_act(void* stream, const fiode_odetrain_config* cfg,
+                                            const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
+                                            const float* x_feat, const float* g_y, float* gx, const float* gx_add,
+                                            const float* gx_add_scale, float* dbg_gft, void* workspace,
+                                            size_t workspace_bytes, int32_t activation);
 
 /* ---- Certification grid (robustness/eval_utils.py:31-89, certify_lipschitz.py:37-143) ------ */
 typedef struct fiode_certify_config {
