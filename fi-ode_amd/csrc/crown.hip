@@ -29,6 +29,8 @@
 //             of one product as the next one's operand, as mlp12_tile); once for the lower rows, once for
 //             the upper ones.
 // Nothing of size [rows][128][128] exists; what leaves the chip is [batch rows][20] floats.
+// GroupSort dynamics (fiode_certify_crown_act): k_crown_fold_gs once per call and k_crown_bounds_gs in
+// k_crown_bounds' place -- the same relaxation on the 64 pair differences of each hidden layer; see there.
 #include "common.h"
 #include "tile.h"
 #include "../../include/fiode.h"
@@ -60,7 +62,30 @@ struct CrownArgs {
   float* out;
   int32_t* exit_iters;
   fiode_crown_debug dbg;
+  float* gs;                // GroupSort only: the folded images (GS_* offsets below), else NULL
 };
+
+// ---- GroupSort (pairs (k, k + H)): d = z[:H] - z[H:], r = relu(d), a = S z + [I; -I] r.
+// The slope-carrying units are the H pair differences of each layer; the skip path S z is affine in
+// eta and is folded once per call by k_crown_fold_gs into these images (floats from CrownArgs::gs):
+//   d1 = A1 eta + c1                         A1 = Delta W1, c1 = Delta u, r1 = eps |A1| 1
+//   d2 = F2 eta + f2 + M2 r1                 M2 = Delta N(W2), [F2 | f2] = Delta (P(W2) [W1 | u] + [0 | b2])
+//   o  = G3 eta + g3 + H3 r1 + N3 r2         H3 = P(W3) N(W2), N3 = N(W3), [G3 | g3] = P(W3) E2 + [0 | b3]
+// with E2 = P(W2) [W1 | u] + [0 | b2].  A1, F2 are stored transposed ([c][k]) as the kernel reads them.
+constexpr int H = M / 2;
+constexpr int LDH = H + 4;            // padded LDS row stride (floats) of the 64-wide images
+constexpr int GS_A1 = 0;              // [C][H]
+constexpr int GS_C1 = GS_A1 + C * H;  // [H]
+constexpr int GS_R1 = GS_C1 + H;      // [H]
+constexpr int GS_M2 = GS_R1 + H;      // [H][H]
+constexpr int GS_F2 = GS_M2 + H * H;  // [C][H]
+constexpr int GS_F2C = GS_F2 + C * H; // [H]
+constexpr int GS_H3 = GS_F2C + H;     // [C][H]
+constexpr int GS_N3 = GS_H3 + C * H;  // [C][H]
+constexpr int GS_G3 = GS_N3 + C * H;  // [C][C]
+constexpr int GS_G3C = GS_G3 + 112;   // [C]
+constexpr int GS_FLOATS = GS_G3C + 16;
+constexpr int WAVEF_GS = 10 * 2 * H + 2 * W1ROWS;   // per-wave arrays [2][H]: dP dM d1 th s1 a1 s2 a2 t2 zc; oc [2][16]
 
 __device__ __forceinline__ uint32_t fkey(float x) {
   const uint32_t b = __float_as_uint(x);
@@ -333,6 +358,299 @@ __global__ __launch_bounds__(64 * NW) void k_crown_bounds(CrownArgs a) {
   }
 }
 
+// The folded GroupSort images, once per call (one workgroup; W2, W1 | u and W3 staged in LDS, E2 kept there).
+__global__ __launch_bounds__(256) void k_crown_fold_gs(CrownArgs a) {
+  if (*a.stop != 0) return;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* Q2s = smem;
+  float* W1T = Q2s + M * LDQ;                       // rows c < C: W1[:, c]; row C: u
+  float* Q3s = W1T + W1ROWS * LDQ;
+  float* E2s = Q3s + W1ROWS * LDQ;                  // [C + 1][LDQ]: rows c < C: E2[:, c]; row C: P(W2) u + b2
+  load_weight_images(a.Q2, a.Q3, Q2s, Q3s, W1ROWS);
+  for (int e = threadIdx.x; e < W1ROWS * M; e += blockDim.x) {
+    const int c = e >> 7, k = e & (M - 1);
+    W1T[c * LDQ + k] = c < C ? a.Q1[k * C + c] : (c == C ? a.u[k] : 0.f);
+  }
+  __syncthreads();
+  float* g = a.gs;
+  for (int e = threadIdx.x; e < (C + 1) * M; e += blockDim.x) {
+    const int c = e >> 7, j = e & (M - 1);
+    float s = 0.f;
+    for (int k = 0; k < M; ++k) s = __fmaf_rn(Q2s[j * LDQ + (k ^ H)], W1T[c * LDQ + k], s);
+    E2s[c * LDQ + j] = c == C ? s + a.b2[j] : s;
+  }
+  for (int e = threadIdx.x; e < C * H; e += blockDim.x) {
+    const int i = e >> 6, k = e & (H - 1);
+    float s = 0.f;
+    for (int j = 0; j < M; ++j) s = __fmaf_rn(Q3s[i * LDQ + (j ^ H)], Q2s[j * LDQ + k] - Q2s[j * LDQ + k + H], s);
+    g[GS_H3 + e] = s;
+    g[GS_N3 + e] = Q3s[i * LDQ + k] - Q3s[i * LDQ + k + H];
+    g[GS_A1 + e] = W1T[i * LDQ + k] - W1T[i * LDQ + k + H];
+  }
+  for (int e = threadIdx.x; e < H * H; e += blockDim.x) {
+    const int j = e >> 6, k = e & (H - 1);
+    g[GS_M2 + e] = (Q2s[j * LDQ + k] - Q2s[j * LDQ + k + H]) - (Q2s[(j + H) * LDQ + k] - Q2s[(j + H) * LDQ + k + H]);
+  }
+  if (threadIdx.x < H) {
+    const int k = threadIdx.x;
+    float r = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) r = r + fabsf(W1T[c * LDQ + k] - W1T[c * LDQ + k + H]);
+    g[GS_C1 + k] = W1T[C * LDQ + k] - W1T[C * LDQ + k + H];
+    g[GS_R1 + k] = a.eps * r;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < (C + 1) * H; e += blockDim.x) {
+    const int c = e >> 6, j = e & (H - 1);
+    g[c < C ? GS_F2 + e : GS_F2C + j] = E2s[c * LDQ + j] - E2s[c * LDQ + j + H];
+  }
+  for (int e = threadIdx.x; e < (C + 1) * C; e += blockDim.x) {
+    const int c = e / C, i = e % C;
+    float s = 0.f;
+    for (int j = 0; j < M; ++j) s = __fmaf_rn(Q3s[i * LDQ + (j ^ H)], E2s[c * LDQ + j], s);
+    if (c < C) g[GS_G3 + i * C + c] = s;
+    else g[GS_G3C + i] = s + a.b3[i];
+  }
+}
+
+// k_crown_bounds for GroupSort: the same three phases on the H pair differences of each layer (one pass
+// of 64 units where ReLU takes two of 64), against the folded images.  The skip terms enter as the
+// initial values of the accumulators: F2 and its centre F2 eta + f2 under the layer-2 products, H3 under
+// K^T = H3^T + M2^T Lambda^T, G3 under the coefficient rows (which also take Lambda F2, one more MFMA per
+// Lambda operand); the constants take Lambda (F2 eta + f2) where ReLU has Lambda b2, and G3 eta + g3 for b3.
+__global__ __launch_bounds__(64 * NW) void k_crown_bounds_gs(CrownArgs a) {
+  if (*a.stop != 0) return;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* M2s = smem;                                // [H][LDH]
+  float* A1T = M2s + H * LDH;                       // [16][LDH] each, rows >= C zero
+  float* F2T = A1T + W1ROWS * LDH;
+  float* H3s = F2T + W1ROWS * LDH;
+  float* N3s = H3s + W1ROWS * LDH;
+  float* G3s = N3s + W1ROWS * LDH;                  // [16][16], zero outside [C][C]
+  float* tab = G3s + W1ROWS * W1ROWS;
+  float* ones = tab + TABF;                         // [H]
+  float* wbase = ones + H;
+  const float* g = a.gs;
+  for (int e = threadIdx.x; e < H * H; e += blockDim.x) M2s[(e >> 6) * LDH + (e & (H - 1))] = g[GS_M2 + e];
+  for (int e = threadIdx.x; e < W1ROWS * H; e += blockDim.x) {
+    const int c = e >> 6, o = c * LDH + (e & (H - 1));
+    const bool in = c < C;
+    A1T[o] = in ? g[GS_A1 + e] : 0.f;
+    F2T[o] = in ? g[GS_F2 + e] : 0.f;
+    H3s[o] = in ? g[GS_H3 + e] : 0.f;
+    N3s[o] = in ? g[GS_N3 + e] : 0.f;
+  }
+  for (int e = threadIdx.x; e < W1ROWS * W1ROWS; e += blockDim.x) {
+    const int i = e >> 4, c = e & 15;
+    G3s[e] = (i < C && c < C) ? g[GS_G3 + i * C + c] : 0.f;
+  }
+  for (int v = threadIdx.x; v < TABF; v += blockDim.x) tab[v] = v <= a.T ? a.etab[v] : 0.f;
+  for (int v = threadIdx.x; v < H; v += blockDim.x) ones[v] = 1.f;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, col = lane & 31;
+  float* wl = wbase + wave * WAVEF_GS;
+  float *dP = wl, *dM = wl + 2 * H, *d1 = wl + 4 * H, *th = wl + 6 * H, *s1 = wl + 8 * H, *a1 = wl + 10 * H,
+        *s2 = wl + 12 * H, *a2 = wl + 14 * H, *t2 = wl + 16 * H, *zc = wl + 18 * H, *oc = wl + 20 * H;
+  const uint32_t rows = a.hi - a.lo;
+  const uint32_t ntiles = (rows + 1) / 2;
+  const int rho = col >> 4, ci = col & 15;
+  for (uint32_t tile = blockIdx.x * NW + wave; tile < ntiles; tile += gridDim.x * NW) {
+    // ---- layer 1 (exact): lane = (row `half`, pairs col + 32 m); the skip centres of d2 and of the outputs
+    {
+      const uint32_t row = a.lo + 2 * tile + half;
+      const uint32_t rr = row < a.hi ? row : a.hi - 1;
+      float h[C];
+      eta_row(a, tab, rr, h);
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {
+        const int k = 32 * m + col;
+        float d = 0.f, z = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          d = __fmaf_rn(A1T[c * LDH + k], h[c], d);
+          z = __fmaf_rn(F2T[c * LDH + k], h[c], z);
+        }
+        d = d + g[GS_C1 + k];
+        const float r = g[GS_R1 + k];
+        float s, t, al;
+        relax(d - r, d + r, s, t, al);
+        const int o = half * H + k;
+        dP[o] = (s + al) * 0.5f;
+        dM[o] = (s - al) * 0.5f;
+        d1[o] = d;
+        th[o] = t * 0.5f;
+        s1[o] = s;
+        a1[o] = al;
+        zc[o] = z + g[GS_F2C + k];
+      }
+      if (col < W1ROWS) {
+        float z = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) z = __fmaf_rn(G3s[col * W1ROWS + c], h[c], z);
+        oc[half * W1ROWS + col] = col < C ? z + g[GS_G3C + col] : 0.f;
+      }
+    }
+    wave_lds_sync();
+    // ---- bounds of the layer-2 pair differences d2 ---------------------------------------------------
+    {
+      const float* pd = ci == C + 1 ? ones : dP + rho * H;
+      const float* md = ci == C + 1 ? ones : dM + rho * H;
+      const float* bm = ci == C ? d1 + rho * H : (ci == C + 1 ? th + rho * H : A1T + ci * LDH);
+      f32x16 P[2], N[2];
+      // registers 8 r .. 8 r + 7 of a lane are row r's columns c = {0..3, 8..11} (half 0) / {4..7, 12..15}:
+      // the skip coefficients F2[j][c] (c < 10) and the skip centre (c = 10) start the sums
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        N[nt] = f16_zero();
+        const int j = 32 * nt + col;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+#pragma unroll
+          for (int e = 0; e < 6; ++e) P[nt][8 * r + e] = F2T[((e & 3) + 8 * (e >> 2) + 4 * half) * LDH + j];
+          P[nt][8 * r + 6] = half == 0 ? zc[r * H + j] : 0.f;
+          P[nt][8 * r + 7] = 0.f;
+        }
+      }
+      const float* q2 = M2s + col * LDH;
+#pragma unroll 1
+      for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+          const int k0 = 32 * kb + 8 * gq + 4 * half;
+          const f32x4 dp = *reinterpret_cast<const f32x4*>(pd + k0);
+          const f32x4 dm = *reinterpret_cast<const f32x4*>(md + k0);
+          const f32x4 bv = *reinterpret_cast<const f32x4*>(bm + k0);
+#pragma unroll
+          for (int nt = 0; nt < 2; ++nt) {
+            const f32x4 q = *reinterpret_cast<const f32x4*>(q2 + 32 * nt * LDH + k0);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+              P[nt] = mfma32(dp[t] * bv[t], q[t], P[nt]);
+              N[nt] = mfma32(dm[t] * bv[t], fabsf(q[t]), N[nt]);
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        const int j = 32 * nt + col;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          float sU = 0.f, sL = 0.f;
+#pragma unroll
+          for (int e = 0; e < 6; ++e) {
+            const float p = P[nt][8 * r + e], n = N[nt][8 * r + e];
+            sU = sU + fabsf(p + n);
+            sL = sL + fabsf(p - n);
+          }
+          const float p6 = P[nt][8 * r + 6], n6 = N[nt][8 * r + 6], p7 = P[nt][8 * r + 7], n7 = N[nt][8 * r + 7];
+          float zU = half == 0 ? (p6 + n6) + (p7 + n7) : 0.f;
+          float zL = half == 0 ? (p6 - n6) + (p7 - n7) : 0.f;
+          sU = sU + shfl_xor32(sU);
+          sL = sL + shfl_xor32(sL);
+          zU = zU + shfl_xor32(zU);
+          zL = zL + shfl_xor32(zL);
+          const float u2 = zU + a.eps * sU;
+          const float l2 = zL - a.eps * sL;
+          float s, t, al;
+          relax(l2, u2, s, t, al);
+          if (half == r) {
+            s2[r * H + j] = s;
+            a2[r * H + j] = al;
+            t2[r * H + j] = t;
+            const uint32_t row = a.lo + 2 * tile + r;
+            if (row < a.hi) {
+              if (a.dbg.l2) a.dbg.l2[(size_t)row * M + j] = l2;      // columns 0..H-1 of the [G][M] arrays
+              if (a.dbg.u2) a.dbg.u2[(size_t)row * M + j] = u2;
+            }
+          }
+        }
+      }
+    }
+    wave_lds_sync();
+    // ---- the ten outputs: lower rows (lu = 0), then upper rows (lu = 1); lane = (rho, i = ci) -----
+    const uint32_t orow = a.lo + 2 * tile + rho;
+#pragma unroll 1
+    for (int lu = 0; lu < 2; ++lu) {
+      f32x16 D2 = f16_zero(), Kt[2];
+      float acc = 0.f;
+#pragma unroll
+      for (int r = 0; r < 8; ++r) D2[r] = G3s[ci * W1ROWS + acc_row(r, half)];
+#pragma unroll
+      for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+          const f32x4 hv = *reinterpret_cast<const f32x4*>(H3s + ci * LDH + 32 * mb + 8 * gq + 4 * half);
+#pragma unroll
+          for (int t = 0; t < 4; ++t) Kt[mb][4 * gq + t] = hv[t];
+        }
+      const float* m2t = M2s + col;
+#pragma unroll 1
+      for (int jb = 0; jb < 2; ++jb) {
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+          const int j0 = 32 * jb + 8 * gq + 4 * half;
+          const f32x4 w3 = *reinterpret_cast<const f32x4*>(N3s + ci * LDH + j0);
+          const f32x4 sv = *reinterpret_cast<const f32x4*>(s2 + rho * H + j0);
+          const f32x4 av = *reinterpret_cast<const f32x4*>(a2 + rho * H + j0);
+          const f32x4 tv = *reinterpret_cast<const f32x4*>(t2 + rho * H + j0);
+          const f32x4 bv = *reinterpret_cast<const f32x4*>(zc + rho * H + j0);
+          const f32x4 fv = col < W1ROWS ? *reinterpret_cast<const f32x4*>(F2T + col * LDH + j0)
+                                        : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const float wp = fmaxf(w3[t], 0.f), wm = fminf(w3[t], 0.f);
+            const float lam = lu ? wp * sv[t] + wm * av[t] : wp * av[t] + wm * sv[t];
+            acc = acc + lam * bv[t];
+            acc = acc + (lu ? wp : wm) * tv[t];
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb) Kt[mb] = mfma32(m2t[(j0 + t) * LDH + 32 * mb], lam, Kt[mb]);
+            D2 = mfma32(fv[t], lam, D2);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      // Kt[mb][r] = K[(rho, i)][k = 32 mb + acc_row(r, half)]
+#pragma unroll
+      for (int mb = 0; mb < 2; ++mb) {
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq) {
+          const int k0 = 32 * mb + 8 * gq + 4 * half;
+          const f32x4 sv = *reinterpret_cast<const f32x4*>(s1 + rho * H + k0);
+          const f32x4 av = *reinterpret_cast<const f32x4*>(a1 + rho * H + k0);
+          const f32x4 zv = *reinterpret_cast<const f32x4*>(d1 + rho * H + k0);
+          const f32x4 tv = *reinterpret_cast<const f32x4*>(th + rho * H + k0);
+          const f32x4 w1 = col < W1ROWS ? *reinterpret_cast<const f32x4*>(A1T + col * LDH + k0)
+                                        : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            const float q = Kt[mb][4 * gq + t];
+            const float qp = fmaxf(q, 0.f), qm = fminf(q, 0.f);
+            const float R = lu ? qp * sv[t] + qm * av[t] : qp * av[t] + qm * sv[t];
+            acc = acc + R * zv[t];
+            acc = acc + (lu ? qp : qm) * (2.0f * tv[t]);
+            D2 = mfma32(w1[t], R, D2);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      // D2[r] = (G3 + Lambda F2 + R A1)[(rho, i)][c = acc_row(r, half)]: c = 0..3, 8, 9 on half 0, 4..7 on half 1
+      float l1 = ((fabsf(D2[0]) + fabsf(D2[1])) + fabsf(D2[2])) + fabsf(D2[3]);
+      if (half == 0) l1 = (l1 + fabsf(D2[4])) + fabsf(D2[5]);
+      l1 = l1 + shfl_xor32(l1);
+      acc = acc + shfl_xor32(acc);
+      if (half == 0 && ci < C && orow < a.hi) {
+        const float bound = (lu ? acc + a.eps * l1 : acc - a.eps * l1) + oc[rho * W1ROWS + ci];
+        a.lbub[(size_t)(orow - a.lo) * (2 * C) + lu * C + ci] = bound;
+        float* dst = lu ? a.dbg.ub : a.dbg.lb;
+        if (dst) dst[(size_t)orow * C + ci] = bound;
+      }
+    }
+    wave_lds_sync();    // the next trip overwrites the arrays this one read
+  }
+}
+
 // barrier lower bound at h (classification.py:224-225)
 __device__ __forceinline__ float barrier_lo(const DynScalars& d, float h) {
   return -d.alpha_1 * (expf(d.sigma_1 * h) - 1.0f);
@@ -477,21 +795,20 @@ inline uint32_t max_batch_rows(int64_t G, int32_t batches) {
   return (uint32_t)(tail > ebs ? tail : ebs);
 }
 
-}  // namespace
-
-extern "C" size_t fiode_certify_crown_workspace_bytes(int64_t G, int32_t batches) {
-  if (G <= 0 || batches <= 0) return 256;
+// the part every activation needs; GroupSort appends the folded images
+inline size_t crown_base_bytes(int64_t G, int32_t batches) {
   const size_t nb = (size_t)batches + 1;
   return al(256) + 2 * al(FIODE_M * 4) + al((size_t)max_batch_rows(G, batches) * 2 * C * 4) + al(nb * 8) + al(nb * 4);
 }
 
-extern "C" int fiode_certify_crown(void* stream, const fiode_crown_config* cfg, const fiode_dyn_config* dyn,
-                                   const fiode_dyn_weights* w, const float* x_feat, const uint8_t* grid, int64_t G,
-                                   float* out, int32_t* exit_iters, int32_t* stop_flag, const fiode_crown_debug* dbg,
-                                   void* workspace, size_t workspace_bytes, int32_t activation) {
+// gs_ok: fiode_certify_crown_act; fiode_certify_crown keeps refusing GroupSort with FIODE_ESHAPE
+int crown_run(void* stream, const fiode_crown_config* cfg, const fiode_dyn_config* dyn, const fiode_dyn_weights* w,
+              const float* x_feat, const uint8_t* grid, int64_t G, float* out, int32_t* exit_iters, int32_t* stop_flag,
+              const fiode_crown_debug* dbg, void* workspace, size_t workspace_bytes, int32_t activation, bool gs_ok) {
   if (!cfg || !dyn || !w || !x_feat || !grid || !out || !workspace) return FIODE_EINVAL;
   if (activation != FIODE_ACT_RELU && activation != FIODE_ACT_GROUPSORT) return FIODE_EINVAL;
-  if (activation == FIODE_ACT_GROUPSORT) return FIODE_ESHAPE;      // the relaxation above is ReLU's
+  if (activation == FIODE_ACT_GROUPSORT && !gs_ok) return FIODE_ESHAPE;
+  const bool gs = activation == FIODE_ACT_GROUPSORT;
   if (dyn->n_hidden != C || dyn->mlp_size != M || dyn->x_dim != FIODE_X) return FIODE_ESHAPE;
   if (cfg->n_classes != C) return FIODE_ESHAPE;
   if (dyn->qp_max_iter < 1 || dyn->qp_max_iter > 32) return FIODE_EINVAL;
@@ -499,7 +816,7 @@ extern "C" int fiode_certify_crown(void* stream, const fiode_crown_config* cfg, 
     return FIODE_EINVAL;
   if (G == 0) return FIODE_OK;
   if (G < cfg->batches || G >= (1LL << 32)) return FIODE_EINVAL;
-  if (workspace_bytes < fiode_certify_crown_workspace_bytes(G, cfg->batches)) return FIODE_EWORKSPACE;
+  if (workspace_bytes < fiode_certify_crown_workspace_bytes_act(G, cfg->batches, activation)) return FIODE_EWORKSPACE;
   CrownArgs a{};
   a.G = (uint32_t)G;
   const uint32_t ebs = (uint32_t)(G / cfg->batches);
@@ -522,7 +839,8 @@ extern "C" int fiode_certify_crown(void* stream, const fiode_crown_config* cfg, 
   a.r1 = reinterpret_cast<float*>(ws + o); o += al(FIODE_M * 4);
   a.lbub = reinterpret_cast<float*>(ws + o); o += al((size_t)max_batch_rows(G, cfg->batches) * 2 * C * 4);
   a.words = reinterpret_cast<uint32_t*>(ws + o); o += al((size_t)(cfg->batches + 1) * 8);
-  a.keys = reinterpret_cast<uint32_t*>(ws + o);
+  a.keys = reinterpret_cast<uint32_t*>(ws + o); o += al((size_t)(cfg->batches + 1) * 4);
+  a.gs = gs ? reinterpret_cast<float*>(ws + o) : nullptr;
   a.own_flag = stop_flag ? 0 : 1;
   a.stop = stop_flag ? stop_flag : own;
   a.out = out;
@@ -533,11 +851,20 @@ extern "C" int fiode_certify_crown(void* stream, const fiode_crown_config* cfg, 
   if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     ncu = 256;
   if (ncu <= 0) ncu = 256;
-  const size_t lds = ((size_t)(M + 2 * W1ROWS) * LDQ + TABF + M + (size_t)NW * WAVEF) * sizeof(float);
-  FIODE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_crown_bounds),
+  const size_t lds = gs ? ((size_t)(H + 4 * W1ROWS) * LDH + W1ROWS * W1ROWS + TABF + H + (size_t)NW * WAVEF_GS) * sizeof(float)
+                        : ((size_t)(M + 2 * W1ROWS) * LDQ + TABF + M + (size_t)NW * WAVEF) * sizeof(float);
+  const auto bounds = gs ? k_crown_bounds_gs : k_crown_bounds;
+  FIODE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bounds),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_crown_prep, dim3(1), dim3(256), 0, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
+  if (gs) {
+    const size_t lds_fold = (size_t)(M + 2 * W1ROWS + C + 1) * LDQ * sizeof(float);
+    FIODE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_crown_fold_gs),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fold));
+    hipLaunchKernelGGL(k_crown_fold_gs, dim3(1), dim3(256), lds_fold, st, a);
+    FIODE_HIP_CHECK(hipGetLastError());
+  }
   for (int b = 0; b < a.nb; ++b) {
     a.b = b;
     a.lo = (uint32_t)b * ebs;
@@ -546,7 +873,7 @@ extern "C" int fiode_certify_crown(void* stream, const fiode_crown_config* cfg, 
     const uint32_t ntiles = (rows + 1) / 2;
     uint32_t blocks = (ntiles + NW - 1) / NW;
     if (blocks > (uint32_t)ncu) blocks = (uint32_t)ncu;        // persistent: one workgroup per CU (LDS)
-    hipLaunchKernelGGL(k_crown_bounds, dim3(blocks), dim3(64 * NW), lds, st, a);
+    hipLaunchKernelGGL(bounds, dim3(blocks), dim3(64 * NW), lds, st, a);
     FIODE_HIP_CHECK(hipGetLastError());
     const dim3 qgrid((rows + 255) / 256);
     hipLaunchKernelGGL(k_crown_qp1, qgrid, dim3(256), 0, st, a);
@@ -557,4 +884,33 @@ extern "C" int fiode_certify_crown(void* stream, const fiode_crown_config* cfg, 
     FIODE_HIP_CHECK(hipGetLastError());
   }
   return FIODE_OK;
+}
+
+}  // namespace
+
+extern "C" size_t fiode_certify_crown_workspace_bytes(int64_t G, int32_t batches) {
+  if (G <= 0 || batches <= 0) return 256;
+  return crown_base_bytes(G, batches);
+}
+
+extern "C" size_t fiode_certify_crown_workspace_bytes_act(int64_t G, int32_t batches, int32_t activation) {
+  if (G <= 0 || batches <= 0 || (activation != FIODE_ACT_RELU && activation != FIODE_ACT_GROUPSORT)) return 256;
+  return crown_base_bytes(G, batches) + (activation == FIODE_ACT_GROUPSORT ? al((size_t)GS_FLOATS * 4) : 0);
+}
+
+extern "C" int fiode_certify_crown(void* stream, const fiode_crown_config* cfg, const fiode_dyn_config* dyn,
+                                   const fiode_dyn_weights* w, const float* x_feat, const uint8_t* grid, int64_t G,
+                                   float* out, int32_t* exit_iters, int32_t* stop_flag, const fiode_crown_debug* dbg,
+                                   void* workspace, size_t workspace_bytes, int32_t activation) {
+  return crown_run(stream, cfg, dyn, w, x_feat, grid, G, out, exit_iters, stop_flag, dbg, workspace, workspace_bytes,
+                   activation, false);
+}
+
+extern "C" int fiode_certify_crown_act(void* stream, const fiode_crown_config* cfg, const fiode_dyn_config* dyn,
+                                       const fiode_dyn_weights* w, const float* x_feat, const uint8_t* grid, int64_t G,
+                                       float* out, int32_t* exit_iters, int32_t* stop_flag,
+                                       const fiode_crown_debug* dbg, void* workspace, size_t workspace_bytes,
+                                       int32_t activation) {
+  return crown_run(stream, cfg, dyn, w, x_feat, grid, G, out, exit_iters, stop_flag, dbg, workspace, workspace_bytes,
+                   activation, true);
 }

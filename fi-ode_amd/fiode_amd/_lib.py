@@ -198,6 +198,10 @@ def _load():
         "fiode_certify_crown": (ct.c_int, [_vp, ct.POINTER(CrownConfig), ct.POINTER(DynConfig),
                                            ct.POINTER(DynWeights), _vp, _vp, ct.c_int64, _vp, _vp, _vp,
                                            ct.POINTER(CrownDebug), _vp, ct.c_size_t, ct.c_int32]),
+        "fiode_certify_crown_workspace_bytes_act": (ct.c_size_t, [ct.c_int64, ct.c_int32, ct.c_int32]),
+        "fiode_certify_crown_act": (ct.c_int, [_vp, ct.POINTER(CrownConfig), ct.POINTER(DynConfig),
+                                               ct.POINTER(DynWeights), _vp, _vp, ct.c_int64, _vp, _vp, _vp,
+                                               ct.POINTER(CrownDebug), _vp, ct.c_size_t, ct.c_int32]),
         "fiode_odetrain_evals": (ct.c_int32, [ct.POINTER(OdeTrainConfig)]),
         "fiode_odetrain_saved_offsets": (ct.c_int, [ct.POINTER(OdeTrainConfig), _vp]),
         "fiode_odetrain_workspace_bytes": (ct.c_size_t, [ct.POINTER(OdeTrainConfig)]),

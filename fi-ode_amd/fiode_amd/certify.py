@@ -121,11 +121,15 @@ def certify_crown(module, images: torch.Tensor, labels: torch.Tensor, T: int = 4
     batch sets it, so a misclassified image costs no certification work and a violated one stops at its
     first violating batch -- with no host read between images.  ``certified_larger_T`` stays 0 (the
     CROWN script has no such variant); ``max_violations`` holds the maximum over the batches that ran
-    (-inf for a skipped image)."""
+    (-inf for a skipped image).
+
+    A GroupSort dynamics is certified inside ``ops.groupsort_crown()`` (the ReLU relaxation on the pair
+    differences); outside it the refusal below stands."""
     dyn = module.dyn_fun
-    if getattr(dyn, "activation_name", "ReLU") != "ReLU":
+    activation = getattr(dyn, "activation_name", "ReLU")
+    if activation != "ReLU" and not (activation == "GroupSort" and ops.GROUPSORT_CROWN):
         raise NotImplementedError("certify_crown: the CROWN relaxation is implemented for activation='ReLU' only "
-                                  "(GroupSort CROWN is out of scope); use certify_lipschitz")
+                                  "(GroupSort CROWN is opt-in: ops.groupsort_crown()); use certify_lipschitz")
     dev = images.device
     if grid is None:
         grid = ops.certify_grid(T, device=dev)

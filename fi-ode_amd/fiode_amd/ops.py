@@ -100,6 +100,25 @@ def groupsort_train_ode(on: bool = True):
         GROUPSORT_TRAIN_ODE, GROUPSORT_TRAINING = before
 
 
+# Opt-in switch of GroupSort CROWN certification (fiode_certify_crown_act with FIODE_ACT_GROUPSORT: the
+# ReLU relaxation on the 64 pair differences of each hidden layer).  Off: every path,
+# message and return value is as without it (``certify_crown_image`` and certify.certify_crown refuse a
+# GroupSort dynamics).  On: both take it; a ReLU dynamics runs as before either way.
+GROUPSORT_CROWN = False
+
+
+@contextlib.contextmanager
+def groupsort_crown(on: bool = True):
+    """Inside: ``GROUPSORT_CROWN = on``; the earlier value is back on exit, after an exception too."""
+    global GROUPSORT_CROWN
+    before = GROUPSORT_CROWN
+    GROUPSORT_CROWN = bool(on)
+    try:
+        yield
+    finally:
+        GROUPSORT_CROWN = before
+
+
 def require_relu(dyn: DynCfg, what: str, lyap_only: bool = False, ode_rk4: bool = False) -> None:
     """The one gate of the training kernels: refuse an activation they do not implement before
     anything is launched.  ReLU passes everywhere.  GroupSort passes with ``lyap_only`` (the caller
@@ -814,9 +833,12 @@ def certify_crown_image(x_feat: torch.Tensor, label: int, grid: torch.Tensor, we
     violation, exit_iters [nb][2] = exits of the lower- and the upper-bound solver call) on the device,
     and with ``debug`` a dict of the per-row arrays lb, ub, f_lb, f_ub [G][10], l2, u2 [G][128] as third
     result.  ``stop_flag``: a device int32 tensor of one element, read and written by the kernels (nonzero
-    on entry: out is all -inf and exit_iters is left as it was, zeros here)."""
+    on entry: out is all -inf and exit_iters is left as it was, zeros here).
+    A GroupSort ``dyn`` is taken while GROUPSORT_CROWN is on (fiode_certify_crown_act); then columns 0..63 of
+    l2, u2 hold the bounds of the layer-2 pair differences z2[:64] - z2[64:] and columns 64..127 stay NaN."""
     act = _act(dyn)
-    if act != L.FIODE_ACT_RELU:
+    groupsort = act == L.FIODE_ACT_GROUPSORT and GROUPSORT_CROWN
+    if act != L.FIODE_ACT_RELU and not groupsort:
         raise NotImplementedError("certify_crown_image: the CROWN relaxation is implemented for activation='ReLU' only")
     dev = grid.device
     G = grid.shape[0]
@@ -835,13 +857,16 @@ def certify_crown_image(x_feat: torch.Tensor, label: int, grid: torch.Tensor, we
         dbg_c = L.CrownDebug(*[dbg_t[n].data_ptr() for n, _ in CROWN_DEBUG_FIELDS])
     ws_w, cw = _weights_c(weights, dev)
     lib = L.lib()
-    ws = _Workspace.get(dev, lib.fiode_certify_crown_workspace_bytes(G, batches), "crown")
+    ws_bytes = (lib.fiode_certify_crown_workspace_bytes_act(G, batches, act) if groupsort
+                else lib.fiode_certify_crown_workspace_bytes(G, batches))
+    ws = _Workspace.get(dev, ws_bytes, "crown")
     cfg = L.CrownConfig(C, int(T), int(batches), int(label), float(eps), float(min_std), int(bool(stop_on_violation)))
     dc = dyn.to_c()
-    rc = lib.fiode_certify_crown(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), x_feat.data_ptr(),
-                                 grid.data_ptr(), G, out.data_ptr(), it.data_ptr(), _ptr(stop_flag),
-                                 ct.byref(dbg_c) if dbg_c is not None else None, ws.data_ptr(), ws.numel(), act)
-    L.check(rc, "fiode_certify_crown")
+    entry = "fiode_certify_crown_act" if groupsort else "fiode_certify_crown"
+    rc = getattr(lib, entry)(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), x_feat.data_ptr(),
+                             grid.data_ptr(), G, out.data_ptr(), it.data_ptr(), _ptr(stop_flag),
+                             ct.byref(dbg_c) if dbg_c is not None else None, ws.data_ptr(), ws.numel(), act)
+    L.check(rc, entry)
     del ws_w
     return (out, it, dbg_t) if debug else (out, it)
 

@@ -487,12 +487,29 @@ FIODE_API size_t fiode_certify_crown_workspace_bytes(int64_t G, int32_t batches)
  * cfg->stop_on_violation the first batch whose maximum is > 0 sets it, and the later batches skip
  * and report -inf (without a caller's flag a word of the workspace serves).  dbg: nullable.
  * Every argument check, the activation included, comes before the workspace check and nothing is
- * launched on an error; FIODE_ACT_GROUPSORT returns FIODE_ESHAPE (the relaxation is ReLU's).
+ * launched on an error; FIODE_ACT_GROUPSORT returns FIODE_ESHAPE here (fiode_certify_crown_act takes it).
  * Ranges as fiode_certify (n = 10, T <= 64, batches <= G < 2^32); G = 0 is a no-op. */
 FIODE_API int fiode_certify_crown(void* stream, const fiode_crown_config* cfg, const fiode_dyn_config* dyn,
                                   const fiode_dyn_weights* w, const float* x_feat, const uint8_t* grid, int64_t G,
                                   float* out, int32_t* exit_iters, int32_t* stop_flag, const fiode_crown_debug* dbg,
                                   void* workspace, size_t workspace_bytes, int32_t activation);
+
+/* The same with the activation as a parameter: FIODE_ACT_RELU (bit-identical to fiode_certify_crown,
+ * outputs and exits) or FIODE_ACT_GROUPSORT; any other value returns FIODE_EINVAL.  GroupSort, pairs
+ * (k, k + 64): with d = z[:64] - z[64:] and r = relu(d) the layer is max = z[64:] + r, min = z[:64] - r
+ * exactly, so the ReLU relaxation (adaptive lower slope, a tie gives 0) is applied to the 64 pair
+ * differences of each hidden layer and the skip path, which is affine in eta, is folded once per call
+ * into the workspace (fiode_certify_crown_workspace_bytes_act: the ReLU size plus the fixed folded
+ * images).  Everything after the bounds is the same.  Under GroupSort dbg->l2 / dbg->u2 keep their
+ * [G][128] shape: columns 0..63 of a row hold the bounds of the layer-2 pair differences d2, columns
+ * 64..127 are not written.  Checks, ranges and the stop flag as fiode_certify_crown.  New symbols only:
+ * FIODE_ABI_VERSION does not move. */
+FIODE_API size_t fiode_certify_crown_workspace_bytes_act(int64_t G, int32_t batches, int32_t activation);
+FIODE_API int fiode_certify_crown_act(void* stream, const fiode_crown_config* cfg, const fiode_dyn_config* dyn,
+                                      const fiode_dyn_weights* w, const float* x_feat, const uint8_t* grid,
+                                      int64_t G, float* out, int32_t* exit_iters, int32_t* stop_flag,
+                                      const fiode_crown_debug* dbg, void* workspace, size_t workspace_bytes,
+                                      int32_t activation);
 
 /* ---- Batched inverse of the Cayley maps (classification.py:282-293 convert_cayley ->
  * cayley(): (I + A)^-1 with A = U - U^H + V^H V; replaces torch.inverse / torch.linalg.inv) ---- */
