@@ -111,6 +111,9 @@ struct LyapArgs {
   float* exp_draws_out;      // optional: the variates used
   uint32_t* kw_out;          // optional: [4][N][4] keep words
   fiode_lyap_grads grads;
+  // the general loss (k_lyap_bwd<A, true> alone reads these; last, so no other member's offset moves)
+  int loss_cand, loss_hinge;   // FIODE_CAND_*, FIODE_HINGE_*
+  float margin_cap;            // cap of kappa * V (+inf: none)
 };
 
 __device__ __forceinline__ uint32_t conv_word(const LyapArgs& a, int pass) {
@@ -367,7 +370,71 @@ __device__ __forceinline__ void store_acc_rows_paired(float* base_row, int w, in
         f32x4{z[4 * g], z[4 * g + 1], z[4 * g + 2], z[4 * g + 3]};
 }
 
-template <Act A>
+// ---- the general loss of k_lyap_bwd<A, true> (fiode_lyap_step_loss; lya_cands.py, pl_modules.py:452-461) ----
+// lc(x) = log(clamp(x, min = 1e-12)) and its derivative (torch.clamp passes the gradient for x >= min)
+__device__ __forceinline__ float lc(float x) { return logf(fmaxf(x, 1e-12f)); }
+__device__ __forceinline__ float dlc(float x) { return x >= 1e-12f ? 1.0f / x : 0.f; }
+
+// V(h) of one row on the simplex and its gradient gv (dense in general; include/fiode.h lists the forms)
+__device__ __forceinline__ float cand_row(int cand, const float (&h)[C], int label, float (&gv)[C]) {
+  float hy = 0.f;
+#pragma unroll
+  for (int j = 0; j < C; ++j) hy = (j == label) ? h[j] : hy;
+  if (cand <= FIODE_CAND_DECISION_BOUNDARY_LOG) {
+    int js = label == 0 ? 1 : 0;
+    float hm = h[js];
+#pragma unroll
+    for (int j = 0; j < C; ++j)
+      if (j != label && h[j] > hm) { hm = h[j]; js = j; }
+    const float lin = (1.0f + hm) - hy;
+    const bool lg = cand == FIODE_CAND_DECISION_BOUNDARY_LOG;
+    const float s = lg ? 1.0f / lin : 1.0f;
+#pragma unroll
+    for (int j = 0; j < C; ++j) gv[j] = (j == js) ? s : ((j == label) ? -s : 0.f);
+    return lg ? logf(lin) : lin;
+  }
+  if (cand == FIODE_CAND_DYN_CROSS_ENTROPY || cand == FIODE_CAND_ONEM_ETAY) {
+    const bool ce = cand == FIODE_CAND_DYN_CROSS_ENTROPY;
+    const float gy = ce ? -dlc(hy) : -1.0f;
+#pragma unroll
+    for (int j = 0; j < C; ++j) gv[j] = (j == label) ? gy : 0.f;
+    return ce ? -lc(hy) : -hy;
+  }
+  // CompositeDynCrossEntropy: the label's lc(1 - h_y) term cancels against mod_prob_y (lya_cands.py:57-70),
+  // so the sum runs over the wrong classes
+  const bool l2 = cand == FIODE_CAND_COMPOSITE_L2;
+  const float ly = lc(hy), dy = dlc(hy);
+  float acc = 0.f;
+#pragma unroll
+  for (int j = 0; j < C; ++j) {
+    const float om = 1.0f - h[j];
+    const float l = lc(om), d = dlc(om);
+    acc += (j == label) ? 0.f : (l2 ? l * l : -l);
+    const float gw = l2 ? (-2.0f * l) * d : d;
+    const float gy = l2 ? (2.0f * ly) * dy : -dy;
+    gv[j] = ((j == label) ? gy : gw) / (float)C;
+  }
+  acc += l2 ? ly * ly : -ly;
+  return acc / (float)C;
+}
+
+// viol = hinge(pre) and d = hinge'(pre): th.relu, F.elu (alpha 1), identity
+__device__ __forceinline__ float hinge_row(int hinge, float pre, float& d) {
+  if (hinge == FIODE_HINGE_RELU) {
+    d = pre > 0.f ? 1.f : 0.f;
+    return pre > 0.f ? pre : 0.f;
+  }
+  if (hinge == FIODE_HINGE_ELU) {
+    d = pre > 0.f ? 1.f : expf(pre);
+    return pre > 0.f ? pre : expm1f(pre);
+  }
+  d = 1.f;
+  return pre;
+}
+
+// GL = false: the DecisionBoundary / ReLU-hinge / uncapped-margin loss, the code it was; GL = true:
+// the loss of a.loss_cand / a.loss_hinge / a.margin_cap in phase A, everything after g_ft the same code
+template <Act A, bool GL = false>
 __global__ __launch_bounds__(256, 1) void k_lyap_bwd(LyapArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Q2s = smem;                         // Q2[i][k] (not transposed)
@@ -446,7 +513,32 @@ __global__ __launch_bounds__(256, 1) void k_lyap_bwd(LyapArgs a) {
         barrier_nominal(a.d, h, ft, lower, nominal, sig, span);
         qp_bisect(lower, nominal, loss_half ? K0 : K1, a.d.tol, v, mu);
         float viol = 0.f, active = 0.f;
-        if (loss_half) {
+        if (GL && loss_half) {
+          // the general loss: dense grad V, capped margin, hinge with its derivative; g goes into
+          // qp_backward_row as the two-non-zero g below
+          float gv[C];
+          const float Vv = cand_row(a.loss_cand, h, label, gv);
+          float Vd = 0.f;                              // jvp of V along f = <grad V(h), f>
+#pragma unroll
+          for (int j = 0; j < C; ++j) Vd += gv[j] * v[j];
+          const float pre = Vd + fminf(kappa * Vv, a.margin_cap);   // the margin carries no gradient
+          float dh;
+          viol = hinge_row(a.loss_hinge, pre, dh);
+          const float gp = dh * a.invN;
+          float g[C], g_nom[C], g_low[C];
+#pragma unroll
+          for (int j = 0; j < C; ++j) g[j] = valid ? gp * gv[j] : 0.f;   // (rows past N: exact zeros, whatever gv holds)
+          qp_backward_row(g, v, mu, nominal, g_nom, g_low);
+#pragma unroll
+          for (int j = 0; j < C; ++j)
+            gft[j] = a.d.scale_nominal ? ((g_nom[j] * span[j]) * (1.0f - sig[j])) * sig[j] : g_nom[j];
+          if (valid) {
+            if (a.V) a.V[row] = Vv;
+            if (a.Vdot) a.Vdot[row] = Vd;
+            if (a.f) store_row10(a.f + (size_t)row * C, v);
+            if (a.g_ftilde) store_row10(a.g_ftilde + (size_t)row * C, gft);
+          }
+        } else if (loss_half) {
           // V = (1 + max_{j != y} h_j) - h_y ; j* first index (lya_cands.py:84-94)
           int js = label == 0 ? 1 : 0;
           float hm = h[js];
@@ -1146,8 +1238,24 @@ extern "C" int fiode_lyap_step(void* stream, const fiode_lyap_config* cfg, const
 extern "C" int fiode_lyap_step_act(void* stream, const fiode_lyap_config* cfg, const fiode_dyn_config* dyn,
                                    const fiode_dyn_weights* w, const fiode_lyap_io* io, fiode_lyap_grads* grads,
                                    void* workspace, size_t workspace_bytes, int32_t activation) {
+  return fiode_lyap_step_loss(stream, cfg, dyn, w, io, grads, workspace, workspace_bytes, activation, nullptr);
+}
+
+extern "C" int fiode_lyap_step_loss(void* stream, const fiode_lyap_config* cfg, const fiode_dyn_config* dyn,
+                                    const fiode_dyn_weights* w, const fiode_lyap_io* io, fiode_lyap_grads* grads,
+                                    void* workspace, size_t workspace_bytes, int32_t activation,
+                                    const fiode_lyap_loss* loss) {
   int rc = check_dyn(dyn);
   if (rc) return rc;
+  // NULL or the default config: the DecisionBoundary / ReLU-hinge kernels (k_lyap_bwd<A, false>)
+  bool general = false;
+  if (loss) {
+    if (loss->candidate < FIODE_CAND_DECISION_BOUNDARY || loss->candidate > FIODE_CAND_COMPOSITE_L2) return FIODE_EINVAL;
+    if (loss->hinge < FIODE_HINGE_RELU || loss->hinge > FIODE_HINGE_IDENTITY) return FIODE_EINVAL;
+    if (loss->margin_cap != loss->margin_cap || loss->reserved != 0) return FIODE_EINVAL;
+    general = !(loss->candidate == FIODE_CAND_DECISION_BOUNDARY && loss->hinge == FIODE_HINGE_RELU &&
+                loss->margin_cap == INFINITY);
+  }
   if (!cfg || !w || !io || !grads || !workspace) return FIODE_EINVAL;
   const int B = cfg->batch, S = cfg->sample_size;
   if (B <= 0 || S <= 0 || (long long)B * S > (1LL << 30)) return FIODE_EINVAL;
@@ -1205,6 +1313,9 @@ extern "C" int fiode_lyap_step_act(void* stream, const fiode_lyap_config* cfg, c
   a.qp_lower = io->qp_lower; a.qp_nominal = io->qp_nominal; a.g_ftilde = io->g_ftilde;
   a.exp_draws = io->exp_draws; a.exp_draws_out = io->exp_draws_out; a.kw_out = io->keep_words_out;
   a.grads = *grads;
+  if (general) {
+    a.loss_cand = loss->candidate; a.loss_hinge = loss->hinge; a.margin_cap = loss->margin_cap;
+  }
 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const bool prof = io->events && io->n_events >= FIODE_LYAP_NKERNELS + 1;
@@ -1237,7 +1348,10 @@ extern "C" int fiode_lyap_step_act(void* stream, const fiode_lyap_config* cfg, c
   else hipLaunchKernelGGL(k_lyap_fwd<RELU>, dim3(fwd_blocks), dim3(64 * FWD_WAVES), lds_fwd, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
   if ((rc = mark())) return rc;
-  if (gs) hipLaunchKernelGGL(k_lyap_bwd<GROUPSORT>, dim3(L.nslab), dim3(256), BWD_LDS, st, a);
+  if (general) {     // the same grid and LDS: only phase A's row math differs
+    if (gs) hipLaunchKernelGGL((k_lyap_bwd<GROUPSORT, true>), dim3(L.nslab), dim3(256), BWD_LDS, st, a);
+    else hipLaunchKernelGGL((k_lyap_bwd<RELU, true>), dim3(L.nslab), dim3(256), BWD_LDS, st, a);
+  } else if (gs) hipLaunchKernelGGL(k_lyap_bwd<GROUPSORT>, dim3(L.nslab), dim3(256), BWD_LDS, st, a);
   else hipLaunchKernelGGL(k_lyap_bwd<RELU>, dim3(L.nslab), dim3(256), BWD_LDS, st, a);
   FIODE_HIP_CHECK(hipGetLastError());
   if ((rc = mark())) return rc;

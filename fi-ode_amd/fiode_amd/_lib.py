@@ -15,6 +15,11 @@ LIB_PATH = pathlib.Path(os.environ.get("FIODE_LIB", _HERE / "libfiode.so"))
 FIODE_SAMPLER_GIVEN, FIODE_SAMPLER_COMPOSITE, FIODE_SAMPLER_DECISION_BOUNDARY, FIODE_SAMPLER_TRAJECTORY = 0, 1, 2, 3
 FIODE_DROPOUT_OFF, FIODE_DROPOUT_GIVEN, FIODE_DROPOUT_PHILOX = 0, 1, 2
 FIODE_ACT_RELU, FIODE_ACT_GROUPSORT = 0, 1     # fiode_*_act: activation of the dynamics MLP
+# fiode_lyap_step_loss: Lyapunov candidate and hinge of the fused step's loss
+(FIODE_CAND_DECISION_BOUNDARY, FIODE_CAND_DECISION_BOUNDARY_LOG, FIODE_CAND_DYN_CROSS_ENTROPY, FIODE_CAND_ONEM_ETAY,
+ FIODE_CAND_COMPOSITE_L1, FIODE_CAND_COMPOSITE_L2) = range(6)
+FIODE_HINGE_RELU, FIODE_HINGE_ELU, FIODE_HINGE_IDENTITY = 0, 1, 2
+FIODE_OK, FIODE_EINVAL, FIODE_ESHAPE, FIODE_EWORKSPACE = 0, 1, 2, 3
 
 class FiodeLibraryError(RuntimeError):
     pass
@@ -50,6 +55,12 @@ class LyapIO(ct.Structure):
                                            "f", "f_log", "qp_lower", "qp_nominal", "g_ftilde", "events")] + \
         [("n_events", ct.c_int32), ("offset_dev", ct.c_void_p), ("exp_draws", ct.c_void_p),
          ("exp_draws_out", ct.c_void_p), ("keep_words_out", ct.c_void_p), ("kappa_dev", ct.c_void_p)]
+
+
+class LyapLoss(ct.Structure):
+    """fiode_lyap_loss (include/fiode.h): margin_cap = +inf is no cap, reserved must be 0."""
+    _fields_ = [("candidate", ct.c_int32), ("hinge", ct.c_int32), ("margin_cap", ct.c_float),
+                ("reserved", ct.c_int32)]
 
 
 LYAP_KERNELS = ("k_static_proj", "k_lyap_prep", "k_lyap_fwd", "k_lyap_bwd", "k_lyap_reduce", "k_lyap_static_grads")
@@ -157,6 +168,9 @@ def _load():
         "fiode_lyap_step_act": (ct.c_int, [_vp, ct.POINTER(LyapConfig), ct.POINTER(DynConfig),
                                            ct.POINTER(DynWeights), ct.POINTER(LyapIO), ct.POINTER(LyapGrads), _vp,
                                            ct.c_size_t, ct.c_int32]),
+        "fiode_lyap_step_loss": (ct.c_int, [_vp, ct.POINTER(LyapConfig), ct.POINTER(DynConfig),
+                                            ct.POINTER(DynWeights), ct.POINTER(LyapIO), ct.POINTER(LyapGrads), _vp,
+                                            ct.c_size_t, ct.c_int32, ct.POINTER(LyapLoss)]),
         "fiode_qp_forward": (ct.c_int, [_vp, ct.c_int32, ct.c_int32, _vp, _vp, ct.c_int32, ct.c_float, _vp, _vp,
                                         _vp, _vp, ct.c_size_t]),
         "fiode_qp_backward": (ct.c_int, [_vp, ct.c_int32, ct.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1,7 +1,8 @@
 """LyapunovLearning with the fused HIP training step (pl_modules.py:338-502).
 
 ``LyapunovLossFn`` is the drop-in for the reference's per-sample autograd graph
-(x_in expand -> sampler -> jvp(DecisionBoundary, eval_dot) -> relu -> mean, pl_modules.py:394-466):
+(x_in expand -> sampler -> jvp(lya_cand, eval_dot) -> hinge -> mean, pl_modules.py:394-466; the
+candidate, the hinge and the margin cap are the plan's ``loss``, an ``ops.LossCfg``):
 one call of ``fiode_lyap_step`` computes the loss, the logging statistics and the gradient of the
 loss w.r.t. the effective dynamics weights and the backbone features; backward() only scales the
 saved gradients by the incoming grad and hands them to autograd, which continues through the
@@ -61,7 +62,8 @@ class LyapunovLossFn(torch.autograd.Function):
             x_feat.detach().contiguous(), y, w, plan["dyn"], sample_size=plan["S"], n_uniform=plan["S1"],
             sampler=plan["sampler"], dropout_mode=plan["dropout_mode"], kappa=plan["kappa"], seed=plan["seed"],
             offset=plan["offset"], h=plan.get("h"), masks=plan.get("masks"), debug=plan.get("debug", False),
-            out=plan.get("out"), offset_dev=plan.get("offset_dev"), kappa_dev=plan.get("kappa_dev"))
+            out=plan.get("out"), offset_dev=plan.get("offset_dev"), kappa_dev=plan.get("kappa_dev"),
+            loss=plan.get("loss"))
         plan["scalars"] = sc
         plan["debug_out"] = dbg
         g = [grads[k] for k in ("x_feat", "Q1", "b1", "Qx", "bx", "Q2", "b2", "Q3", "b3")]
@@ -224,7 +226,8 @@ class LyapODELossFn(torch.autograd.Function):
             xf, y, w, plan["dyn"], sample_size=plan["S"], n_uniform=plan["S1"],
             sampler=plan["sampler"], dropout_mode=plan["dropout_mode"], kappa=plan["kappa"], seed=plan["seed"],
             offset=plan["offset"], h=plan.get("h"), masks=plan.get("masks"), debug=plan.get("debug", False),
-            out=plan.get("out"), offset_dev=plan.get("offset_dev"), kappa_dev=plan.get("kappa_dev"))
+            out=plan.get("out"), offset_dev=plan.get("offset_dev"), kappa_dev=plan.get("kappa_dev"),
+            loss=plan.get("loss"))
         plan["scalars"] = sc
         plan["debug_out"] = dbg
         ctx.lyap = [grads[k] for k in ("x_feat", "Q1", "b1", "Qx", "bx", "Q2", "b2", "Q3", "b3")]
@@ -317,6 +320,97 @@ class DecisionBoundary(nn.Module):
         return torch.log(v) if self.log_mode else v
 
 
+def _log_clamped(p):
+    return torch.log(torch.clamp(p, min=1e-12))
+
+
+class DynCrossEntropy(nn.Module):
+    """lya_cands.py:5-18: the label's cross entropy, -log(max(h_y, 1e-12)) on the simplex."""
+
+    def __init__(self, on_simplex=False):
+        super().__init__()
+        self.on_simplex = on_simplex
+
+    def forward(self, state_output, y):
+        if self.on_simplex:
+            return F.nll_loss(_log_clamped(state_output), y, reduction="none")
+        return F.cross_entropy(state_output, y, reduction="none")
+
+
+class MSELoss(nn.Module):
+    """lya_cands.py:20-28: squared distance to the one-hot label, per class ([N, C]: not a per-row
+    candidate, so the fused training step refuses it)."""
+
+    def __init__(self, on_simplex=False, num_class=10):
+        super().__init__()
+        self.on_simplex, self.num_class = on_simplex, num_class
+
+    def forward(self, state_output, y):
+        assert self.on_simplex, "States need to be on simplex"
+        return F.mse_loss(state_output, F.one_hot(y, self.num_class).float(), reduction="none")
+
+
+class OnemEtay(nn.Module):
+    """lya_cands.py:31-44: -h_y on the simplex."""
+
+    def __init__(self, on_simplex=False):
+        super().__init__()
+        self.on_simplex = on_simplex
+
+    def forward(self, state_output, y):
+        if self.on_simplex:
+            return F.nll_loss(state_output, y, reduction="none")
+        return F.cross_entropy(state_output, y, reduction="none")
+
+
+class CompositeDynCrossEntropy(nn.Module):
+    """lya_cands.py:46-70: with l_j = -log(max(1 - h_j, 1e-12)) and l_y' = -log(max(h_y, 1e-12)),
+    'L1': (sum_j l_j - l_y + l_y') / C;  'L2': (sum_j l_j^2 - l_y^2 + l_y'^2) / C."""
+
+    def __init__(self, on_simplex=False, norm_type="L1"):
+        super().__init__()
+        assert norm_type in ("L1", "L2"), "Invalid Norm Type"
+        self.on_simplex, self.norm_type = on_simplex, norm_type
+
+    def forward(self, state_output, y):
+        prob = state_output if self.on_simplex else F.softmax(state_output, dim=1)
+        prob_y = torch.gather(prob, 1, y[:, None])[:, 0]
+        wrong_terms = -_log_clamped(1 - prob)
+        if self.norm_type == "L2":
+            label_term = _log_clamped(prob_y) ** 2 - _log_clamped(1 - prob_y) ** 2
+            return ((wrong_terms ** 2).sum(dim=-1) + label_term) / prob.shape[1]
+        label_term = _log_clamped(1 - prob_y) - _log_clamped(prob_y)
+        return (wrong_terms.sum(dim=1) + label_term) / prob.shape[1]
+
+
+def fused_candidate(lya_cand: nn.Module) -> str:
+    """The ``ops.LossCfg`` candidate name of a Lyapunov candidate module, or NotImplementedError with the
+    reason the fused training step does not take it.  Exact types: a subclass may compute something else."""
+    t = type(lya_cand)
+    if t is DecisionBoundary:
+        if not lya_cand.log_mode:
+            return "DecisionBoundary"       # (either on_simplex: the step's samples are on the simplex)
+        if not lya_cand.on_simplex:
+            raise NotImplementedError("DecisionBoundary(log_mode=True, on_simplex=False): the softmax path is "
+                                      "not fused")
+        return "DecisionBoundaryLog"
+    if t is MSELoss:
+        raise NotImplementedError("MSELoss yields a [N, C] violation, not a per-row one: the fused training "
+                                  "step does not take it")
+    names = {DynCrossEntropy: "DynCrossEntropy", OnemEtay: "OnemEtay", CompositeDynCrossEntropy: "Composite"}
+    if t not in names:
+        raise NotImplementedError(f"lya_cand {t.__name__}: the fused training step implements DecisionBoundary, "
+                                  "DynCrossEntropy, OnemEtay and CompositeDynCrossEntropy")
+    if not lya_cand.on_simplex:
+        raise NotImplementedError(f"{t.__name__}(on_simplex=False): the softmax path is not fused")
+    return names[t] + lya_cand.norm_type if t is CompositeDynCrossEntropy else names[t]
+
+
+def fused_hinge(act) -> str:
+    """compute_loss's ``act`` (pl_modules.py:456-461): 'relu', 'elu', anything else the identity."""
+    return act if act in ("relu", "elu") else "identity"
+
+
 class UniformInitFun(nn.Module):
     """dynamics/init_coordinates.py:38-44: h0 = 1/C, static = param_map(x)."""
 
@@ -336,7 +430,8 @@ class UniformInitFun(nn.Module):
 
 
 class LyapunovLearning(nn.Module):
-    """pl_modules.py:338-502 (order=1, act='relu', DecisionBoundary candidate)."""
+    """pl_modules.py:338-502 (order=1; the loss follows ``lya_cand``, ``act`` and ``relax_exp_stable`` /
+    ``scaleLeps``: ``loss_cfg``)."""
 
     def __init__(self, order, h_sample_size, h_dist_lim, sampler: CompositeSampler,
                  sampler_scheduler: CompositeSamplerScheduler, dynamics: OrthoClassDynProjectSimplexLips,
@@ -350,11 +445,11 @@ class LyapunovLearning(nn.Module):
         super().__init__()
         if order != 1:
             raise NotImplementedError("order=1 (the reference raises for order 0; higher orders are unused)")
-        if act != "relu":
-            raise NotImplementedError("act='relu' is the README configuration")
-        if barrier_loss or lips_train or relax_exp_stable or adv_train:
-            raise NotImplementedError("barrier_loss / lips_train / relax_exp_stable / adv_train are off "
-                                      "in the north-star configuration and not fused")
+        if barrier_loss:
+            raise NotImplementedError("barrier_loss needs a third MLP pass with fresh dropout masks: not fused")
+        if lips_train or adv_train:
+            raise NotImplementedError("lips_train / adv_train are off in the north-star configuration and not fused")
+        self.relax_exp_stable, self.scaleLeps = bool(relax_exp_stable), scaleLeps
         self.train_ode, self.train_ode_epoch = bool(train_ode), int(train_ode_epoch)
         self.order, self.h_sample_size, self.h_dist_lim = order, h_sample_size, h_dist_lim
         self.sampler, self.sampler_scheduler = sampler, sampler_scheduler
@@ -363,6 +458,7 @@ class LyapunovLearning(nn.Module):
                          output_fun=output if output is not None else DefaultOutputFun(), ode_tol=train_ode_tol,
                          ts=torch.linspace(0, t_max, 2))
         self.lya_cand = lya_cand if lya_cand is not None else DecisionBoundary(on_simplex=True)
+        fused_candidate(self.lya_cand)      # a candidate the fused step does not take: refused here already
         self.t_max = t_max
         self.use_adjoint = False
         self.train_ode_solver, self.train_ode_tol = train_ode_solver, train_ode_tol
@@ -548,8 +644,18 @@ class LyapunovLearning(nn.Module):
         return torch.where(step < L_, step / L_ * float(dyn.kappa),
                            torch.full_like(step, float(dyn.kappa))).float()
 
+    def loss_cfg(self, act: Optional[str] = None) -> ops.LossCfg:
+        """The fused step's loss (pl_modules.py:452-461): the candidate of ``self.lya_cand``, the hinge of
+        ``act`` (default ``self.act``) and, with ``relax_exp_stable``, the margin cap scaleLeps * alpha_1 *
+        eps in Python floats.  NotImplementedError for a candidate the step does not take
+        (``fused_candidate``)."""
+        cap = None
+        if self.relax_exp_stable:
+            cap = self.scaleLeps * self.dyn_fun.alpha_1 * self.eps
+        return ops.LossCfg(fused_candidate(self.lya_cand), fused_hinge(self.act if act is None else act), cap)
+
     def step_plan(self, y: torch.Tensor, h: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None,
-                  debug: bool = False, static_state: Optional[torch.Tensor] = None) -> dict:
+                  debug: bool = False, static_state: Optional[torch.Tensor] = None, act: str = "relu") -> dict:
         mix = self.sampler_scheduler.get_mixer_coefficients(self.current_epoch)
         for i, m in enumerate(mix):
             self.log(f"mixing_weight_{i}", float(m))
@@ -566,7 +672,7 @@ class LyapunovLearning(nn.Module):
         plan = dict(dyn=self.dyn_fun.dyn_cfg(), S=self.h_sample_size, S1=s1, sampler=kind, dropout_mode=drop,
                     kappa=self.current_kappa(), kappa_dev=self.kappa_device(), seed=self.seed,
                     offset=self._rng_offset if self.rng_counter is None else 0, h=h, masks=masks,
-                    debug=debug, out=None, offset_dev=self.rng_counter)
+                    debug=debug, out=None, offset_dev=self.rng_counter, loss=self.loss_cfg(act))
         self._rng_offset += 1
         return plan
 
@@ -618,11 +724,12 @@ class LyapunovLearning(nn.Module):
     def compute_loss(self, x, y, batch_size=None, act="relu", h=None, masks=None, debug=False):
         """pl_modules.py:390-502 with the per-sample graph fused (LyapunovLossFn)."""
         self.require_trainable_dynamics("LyapunovLearning.compute_loss", step=True)
+        self.loss_cfg(act)      # a candidate the fused step does not take raises before any tensor is touched
         step_stream = torch.cuda.current_stream(x.device) if x.is_cuda else None
         with self.streams.scope(step_stream):
-            return self._compute_loss(x, y, h=h, masks=masks, debug=debug)
+            return self._compute_loss(x, y, h=h, masks=masks, debug=debug, act=act)
 
-    def _compute_loss(self, x, y, h=None, masks=None, debug=False):
+    def _compute_loss(self, x, y, h=None, masks=None, debug=False, act="relu"):
         if self.current_epoch == self.epoch_off_scale:
             self.dyn_fun.scale_nominal = False
         if self.parallel_cayley and self.training and x.is_cuda and self.dyn_fun.cayley:
@@ -631,7 +738,7 @@ class LyapunovLearning(nn.Module):
         bb = self.init_coordinates.param_map
         if isinstance(bb, torch.nn.Sequential) and getattr(bb[-1], "after_conv_hook", None) is not None:
             bb[-1].after_conv_hook = None       # never left armed for a later (e.g. validation) forward
-        plan = self.step_plan(y, h=h, masks=masks, debug=debug, static_state=static_state)
+        plan = self.step_plan(y, h=h, masks=masks, debug=debug, static_state=static_state, act=act)
         w = self.dyn_fun.effective_weights()
         ode_on = self.train_ode and self.current_epoch > self.train_ode_epoch
         if (ode_on and self.fused_ode_loss and static_state.is_cuda and self.simplex and y.dtype == torch.int64

@@ -206,6 +206,41 @@ class _Workspace:
         cls._arena[dev.index] = [torch.zeros(slots * nb, dtype=torch.uint8, device=dev), nb, 0]
 
 
+CANDIDATES = {"DecisionBoundary": L.FIODE_CAND_DECISION_BOUNDARY,
+              "DecisionBoundaryLog": L.FIODE_CAND_DECISION_BOUNDARY_LOG,
+              "DynCrossEntropy": L.FIODE_CAND_DYN_CROSS_ENTROPY, "OnemEtay": L.FIODE_CAND_ONEM_ETAY,
+              "CompositeL1": L.FIODE_CAND_COMPOSITE_L1, "CompositeL2": L.FIODE_CAND_COMPOSITE_L2}
+HINGES = {"relu": L.FIODE_HINGE_RELU, "elu": L.FIODE_HINGE_ELU, "identity": L.FIODE_HINGE_IDENTITY}
+
+
+@dataclass(frozen=True)
+class LossCfg:
+    """Mirror of fiode_lyap_loss: the loss of the fused step (fiode_lyap_step_loss).  ``candidate``: a
+    key of CANDIDATES (the Lyapunov candidate with on_simplex=True; 'DecisionBoundaryLog' is log_mode,
+    'CompositeL1' / 'CompositeL2' the norm_type of CompositeDynCrossEntropy); ``hinge``: a key of HINGES;
+    ``margin_cap``: the cap of kappa * V (relax_exp_stable), None = no cap."""
+    candidate: str = "DecisionBoundary"
+    hinge: str = "relu"
+    margin_cap: Optional[float] = None
+
+    def __post_init__(self):
+        if self.candidate not in CANDIDATES:
+            raise ValueError(f"candidate {self.candidate!r}: the fused step implements {sorted(CANDIDATES)}")
+        if self.hinge not in HINGES:
+            raise ValueError(f"hinge {self.hinge!r}: the fused step implements {sorted(HINGES)}")
+        if self.margin_cap is not None and self.margin_cap != self.margin_cap:
+            raise ValueError("margin_cap is NaN")
+
+    @property
+    def is_default(self) -> bool:
+        return (self.candidate == "DecisionBoundary" and self.hinge == "relu" and
+                (self.margin_cap is None or self.margin_cap == float("inf")))
+
+    def to_c(self) -> L.LyapLoss:
+        cap = float("inf") if self.margin_cap is None else float(self.margin_cap)
+        return L.LyapLoss(CANDIDATES[self.candidate], HINGES[self.hinge], cap, 0)
+
+
 def _weights_c(w: Dict[str, torch.Tensor], dev) -> tuple:
     ws = {k: _need(w[k], k, WEIGHT_SHAPES[k], torch.float32, dev) for k in WEIGHT_KEYS}
     return ws, L.DynWeights(*[ws[k].data_ptr() for k in WEIGHT_KEYS])
@@ -228,8 +263,11 @@ def lyap_step(x_feat: torch.Tensor, y: torch.Tensor, weights: Dict[str, torch.Te
               dropout_mode: int = L.FIODE_DROPOUT_PHILOX, kappa: float = 2.0, seed: int = 0, offset: int = 0,
               h: Optional[torch.Tensor] = None, masks: Optional[torch.Tensor] = None, debug: bool = False,
               out: Optional[dict] = None, events=None, offset_dev: Optional[torch.Tensor] = None,
-              exp_draws: Optional[torch.Tensor] = None, kappa_dev: Optional[torch.Tensor] = None):
+              exp_draws: Optional[torch.Tensor] = None, kappa_dev: Optional[torch.Tensor] = None,
+              loss: Optional[LossCfg] = None):
     """The fused training step (fiode_lyap_step_act).  Returns (scalars[8], grads dict, debug dict).
+    ``loss``: the step's loss (LossCfg: candidate, hinge, margin cap; fiode_lyap_step_loss).  None or the
+    default config (DecisionBoundary, relu, no cap) takes fiode_lyap_step_act as before.
     ``dyn.activation``: 'ReLU', or 'GroupSort' while ``GROUPSORT_TRAINING`` is on (require_relu).
     ``events``: optional list of len(_lib.LYAP_KERNELS)+1 torch.cuda.Event(enable_timing=True),
     recorded by the library around each of its kernels on the current stream.
@@ -241,6 +279,8 @@ def lyap_step(x_feat: torch.Tensor, y: torch.Tensor, weights: Dict[str, torch.Te
     (``exp_draws``) and the dropout keep words (``keep_words`` int32 [4, N, 4])."""
     require_relu(dyn, "lyap_step", lyap_only=True)
     act = _act(dyn)
+    if loss is not None and not isinstance(loss, LossCfg):
+        raise TypeError(f"loss: expected ops.LossCfg, got {type(loss).__name__}")
     dev = x_feat.device
     B = x_feat.shape[0]
     S = int(sample_size)
@@ -314,6 +354,16 @@ def lyap_step(x_feat: torch.Tensor, y: torch.Tensor, weights: Dict[str, torch.Te
     lib = L.lib()
     nbytes = lib.fiode_lyap_workspace_bytes(ct.byref(cfg), ct.byref(dc))
     ws = _Workspace.get(dev, nbytes, "lyap")
+    if loss is not None and not loss.is_default:
+        if not hasattr(lib, "fiode_lyap_step_loss"):
+            raise L.FiodeLibraryError(f"{L.LIB_PATH} has no fiode_lyap_step_loss: it implements the default loss only")
+        cl = loss.to_c()
+        rc = lib.fiode_lyap_step_loss(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), ct.byref(io),
+                                      ct.byref(cg), ct.c_void_p(ws.data_ptr()), ct.c_size_t(ws.numel()), act,
+                                      ct.byref(cl))
+        L.check(rc, "fiode_lyap_step_loss")
+        del ws_w
+        return scalars, grads, dbg
     if act == L.FIODE_ACT_RELU and not hasattr(lib, "fiode_lyap_step_act"):
         # an older build under an A/B (FIODE_LIB, _lib._load): its fiode_lyap_step is the ReLU case
         rc = lib.fiode_lyap_step(_stream(dev), ct.byref(cfg), ct.byref(dc), ct.byref(cw), ct.byref(io),

@@ -194,6 +194,46 @@ FIODE_API int fiode_lyap_step_act(void* stream, const fiode_lyap_config* cfg, co
                                   const fiode_dyn_weights* w, const fiode_lyap_io* io, fiode_lyap_grads* grads,
                                   void* workspace, size_t workspace_bytes, int32_t activation);
 
+/* fiode_lyap_step_act with the loss as a parameter (pl_modules.py:403-466, lya_cands.py).  Per row,
+ * with h on the simplex, y its label and f the QP output of the loss pass:
+ *   Vdot = <grad V(h), f>,  margin = min(kappa V, margin_cap) (no gradient through it),
+ *   pre = Vdot + margin,  viol = hinge(pre),  loss = mean(viol),  eff = #(viol > 0),
+ *   d loss / d f = hinge'(pre) / N * grad V(h).
+ * Candidates, all on the simplex (on_simplex=True); lc(x) = log(max(x, 1e-12)), lc'(x) = 1 / x for
+ * x >= 1e-12 and 0 below (torch.clamp's gradient); j* = the first index of max_{j != y} h_j; C = 10:
+ *   DECISION_BOUNDARY      V = (1 + h_j*) - h_y                                    (log_mode False)
+ *   DECISION_BOUNDARY_LOG  V = log((1 + h_j*) - h_y)                               (log_mode True)
+ *   DYN_CROSS_ENTROPY      V = -lc(h_y)
+ *   ONEM_ETAY              V = -h_y
+ *   COMPOSITE_L1           V = (-sum_{j != y} lc(1 - h_j) - lc(h_y)) / C           (norm_type 'L1')
+ *   COMPOSITE_L2           V = (sum_{j != y} lc(1 - h_j)^2 + lc(h_y)^2) / C        (norm_type 'L2')
+ * Hinges: RELU; ELU (alpha 1: pre > 0 ? pre : expm1(pre)); IDENTITY (viol = pre).
+ * margin_cap = +inf: no cap (relax_exp_stable False).
+ * loss == NULL, or {DECISION_BOUNDARY, RELU, +inf, 0}, IS fiode_lyap_step_act: the same kernels and
+ * bits.  An unknown candidate or hinge, a NaN margin_cap or a non-zero `reserved` is FIODE_EINVAL;
+ * the other rules are fiode_lyap_step_act's (every argument check before the workspace-size check,
+ * nothing launched on an error, workspace = fiode_lyap_workspace_bytes).  A new symbol only:
+ * FIODE_ABI_VERSION does not move. */
+enum {
+  FIODE_CAND_DECISION_BOUNDARY = 0,
+  FIODE_CAND_DECISION_BOUNDARY_LOG = 1,
+  FIODE_CAND_DYN_CROSS_ENTROPY = 2,
+  FIODE_CAND_ONEM_ETAY = 3,
+  FIODE_CAND_COMPOSITE_L1 = 4,
+  FIODE_CAND_COMPOSITE_L2 = 5
+};
+enum { FIODE_HINGE_RELU = 0, FIODE_HINGE_ELU = 1, FIODE_HINGE_IDENTITY = 2 };
+typedef struct fiode_lyap_loss {
+  int32_t candidate;   /* FIODE_CAND_*                          */
+  int32_t hinge;       /* FIODE_HINGE_*                         */
+  float margin_cap;    /* cap of kappa * V; +inf = no cap       */
+  int32_t reserved;    /* must be 0                             */
+} fiode_lyap_loss;
+FIODE_API int fiode_lyap_step_loss(void* stream, const fiode_lyap_config* cfg, const fiode_dyn_config* dyn,
+                                   const fiode_dyn_weights* w, const fiode_lyap_io* io, fiode_lyap_grads* grads,
+                                   void* workspace, size_t workspace_bytes, int32_t activation,
+                                   const fiode_lyap_loss* loss);
+
 /* The vector-Jacobian product of fiode_dyn_eval_act (the reference's eval_dot is an ordinary
  * differentiable torch function, classification.py:104-126): given g_f [N][C] = d L / d f it writes
  * g_h [N][C] = d L / d h and, into `grads` (all members required, overwritten), d L / d (effective
